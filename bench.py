@@ -14,6 +14,11 @@ device-resident when the timed region starts (N > 1: every slab's planes on its 
 N > 1: the SAME box is split into N slabs along x (strong scaling, as BASELINE.json's metric asks: one problem at 1/2/4/8
 GPUs); super-droplets that cross a slab face are handed to the neighbouring device (no collective).
 --oversubscribe maps all N slabs to device 0 (what a one-GPU box can measure of the N-slab protocol).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, dtype, config).
+--full adds everything else this script measures: the roofline and the stage table (their own hipEvents and extra steps), the device's
+copy bandwidth, the legs (other arithmetic, host arrays, coal-stress, soak, activation, C2, C5) and the CPU baseline.
+--dump-outputs DIR writes the caller's th and rv after the last timed step as DIR/th.npy and DIR/rv.npy.
 """
 import argparse
 import json
@@ -206,6 +211,23 @@ def cpu_baseline(args):
                                         "sample": "the reference's thrust::omp backend, 64^3-class box, build container, BASELINE.md section 2"}}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=1234):
+    """writes {name: float32 / float64 array} as out_dir/<name>.npy.  If together they would hold more than DUMP_BYTES, every array is cut
+    to a sample of its flattened elements, in ascending index order, that depends only on the seed and its size: two runs with the
+    same arguments write the same elements (the headline box's th and rv, 2 x 16.8 MB, are written whole)"""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def c2_leg(lgrngn, torch, steps=60, warmup=10, real_t=np.float32, **change):
     """BASELINE configs[1] timed: 76 x 76 cells x 64 super-droplets, sstp 10 / 10, float, icicle's call (th, rv as host arrays in every
     step).  3.7e5 super-droplets and twenty substeps: what a step costs here is its launches and host waits, so both are counted"""
@@ -312,6 +334,13 @@ def main():
     ap.add_argument("--dbg", default="",
                     help="comma-separated names of opts_init.dbg_flags bits (libcloudphxx_amd.lgrngn.dbg: test / measurement switches, "
                          "e.g. NO_DEFERRED_SORT,COND_SORTED_ORDER,MULTI_SERIALIZE); the library reads no such switch from the environment")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the condensation stage's events in the timed region, the stage pass, the roofline "
+                         "and the device's copy bandwidth, the coal-stress figures, the legs and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the caller holds after the last one -- th and rv, which step_sync updates in "
+                         "place -- as DIR/th.npy and DIR/rv.npy (see dump_outputs)")
     args = ap.parse_args()
 
     # stdout carries ONE line, the result.  Libraries that write to file descriptor 1 on their own (RCCL prints a version banner from
@@ -334,6 +363,9 @@ def main():
     if args.self_ring and (world > 1 or args.gpus > 1):
         raise SystemExit("--self-ring is the one-rank form of the one-object-per-rank path: no launcher, --gpus 1")
     spmd = (world > 1 and not args.native) or args.self_ring
+    if args.dump_outputs and spmd and world > 1:
+        raise SystemExit("--dump-outputs needs the whole box in one process: --gpus N without a launcher, or --native under one")
+    stage_timers = args.full and not args.no_stage_timers
     native_multi = args.gpus > 1 and not spmd
     idle = native_multi and rank > 0
     n_slabs = args.gpus
@@ -555,8 +587,8 @@ def main():
         p1 = prt.prt if spmd else prt
         # the timed region carries the events of the dominant kernel's stage only (the roofline's launch duration, two records per
         # step); the stage table comes from a few EXTRA steps with every stage's events on -- each record is a packet between two kernels,
-        # and fifty of them per step cost a 16-plane slab 0.11 ms of its 1.33 ms step (0.04 of C3's 10)
-        if not args.no_stage_timers:
+        # and fifty of them per step cost a 16-plane slab 0.11 ms of its 1.33 ms step (0.04 of C3's 10).  Both only with --full.
+        if stage_timers:
             p1.set_profiling(2)
         barrier()
         n_part_start = p1.n_part
@@ -567,17 +599,22 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         n_part_end = p1.n_part
-        tm_ = p1.timings() if not args.no_stage_timers else {}
+        if args.dump_outputs:
+            if spmd and world > 1:                           # (the native object failed under a launcher: every rank holds a slab)
+                raise SystemExit("--dump-outputs: the native multi_HIP object failed, every rank holds only its own slab")
+            slabs = fields_t if native_multi else [fields_t]      # (native multi_HIP: th and rv in per-slab pieces, joined along x)
+            dump_outputs(args.dump_outputs, {nm: np.concatenate([s[k].cpu().numpy() for s in slabs]) for k, nm in ((0, "th"), (1, "rv"))})
+        tm_ = p1.timings() if stage_timers else {}
         cond_ms = tm_.get("cond")
         listed_ms_total = tm_.get("cond_listed")
         stage_ms = {}
-        if not args.no_stage_timers and args.stage_steps > 0:
+        if stage_timers and args.stage_steps > 0:
             p1.set_profiling(1)
             for _ in range(args.stage_steps):
                 one_step()
             sync_all()                                       # (no rendezvous with the other ranks: they are in the same loop, or idle)
             stage_ms = {k: (v * args.steps / args.stage_steps if k != "rendezvous_hidden_share" else v) for k, v in p1.timings().items()}
-        if not args.no_stage_timers:
+        if stage_timers:
             p1.set_profiling(0)
         if cond_ms is not None:
             stage_ms["cond"] = cond_ms                       # (the timed region's own)
@@ -671,15 +708,17 @@ def main():
                                                  "lane_util": lane,
                                                  "wave_insts_per_launch": t["valu_insts"], "f64_insts_per_launch": f64, "source": src}
         # attainable HBM bandwidth on this device (device-to-device copy of 1 GiB, read + write), SURVEY 8(d)
-        a_ = torch.empty(1 << 30, dtype=torch.uint8, device=dev); b_ = torch.empty_like(a_)
-        b_.copy_(a_); torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            b_.copy_(a_)
-        e1.record(); torch.cuda.synchronize()
-        copy_gbs = 10 * 2 * a_.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del a_, b_
+        copy_gbs = None
+        if args.full:
+            a_ = torch.empty(1 << 30, dtype=torch.uint8, device=dev); b_ = torch.empty_like(a_)
+            b_.copy_(a_); torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                b_.copy_(a_)
+            e1.record(); torch.cuda.synchronize()
+            copy_gbs = 10 * 2 * a_.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del a_, b_
         # per-stage achieved algorithmic bandwidth (bytes per SD from SURVEY 8(d) with 4-byte indices: I = 4)
         I = 4
         stage_bytes = {"cond": 5 * R + 2 * I + 8, "cond_cellfinish": (1 if not args.strict_fp else 2) * R, "hskpng_vterm_all": 2 * R + I,
@@ -692,7 +731,7 @@ def main():
         stage_ms_r["re-sort (post_copy + in-cell shuffle)"] = sort_ms
         stage_roof = {}
         coal_stress = None
-        if args.workload == "coal-stress" and world_out == 1 and not args.self_ring:
+        if args.full and args.workload == "coal-stress" and world_out == 1 and not args.self_ring:
             # pairs that collided in the last step: the living super-droplets that carry coalescence's invalid terminal velocity
             # (the one of each pair that grew); a collided pair writes back N + 3R bytes (n of the one, rw2, rd3, vt of the other)
             pairs = int(p1.state_u64("raw_collided")[0])
@@ -740,15 +779,19 @@ def main():
                                   "fp64, growth rate as one rational expression + FMA; " + ("lean bracketed secant to the reference's tolerance 2^-15" if args.cond_solver == "lean"
                                                                                              else "the reference's TOMS748 iterates"),
                        "init_s": t_init},
-            "roofline": roof,
-            # `cond` from the timed region; the other stages from args.stage_steps extra steps (scaled to the same per-step unit)
-            "stage_ms_per_step": {k: (v / args.steps if k != "rendezvous_hidden_share" else v) for k, v in stage_ms.items()},
-            "stage_pass_steps": 0 if args.no_stage_timers else args.stage_steps,
-            # (the stage pass times the stages ONE AFTER THE OTHER.  In the timed region the in-cell ranking -- most of post_copy -- runs on a
-            # stream of its own next to cond_cellfinish, sync_out, hskpng_Tpr and hskpng_vterm_all, so the stages add up to more than ms_per_step)
-            "stage_note": "stages timed serially by the stage pass; in the timed region post_copy's in-cell ranking overlaps cond_cellfinish .. hskpng_vterm_all",
-            "stage_roofline": stage_roof,
         }
+        if args.full:
+            out.update({
+                "roofline": roof,
+                # `cond` from the timed region; the other stages from args.stage_steps extra steps (scaled to the same per-step unit)
+                "stage_ms_per_step": {k: (v / args.steps if k != "rendezvous_hidden_share" else v) for k, v in stage_ms.items()},
+                "stage_pass_steps": args.stage_steps if stage_timers else 0,
+                # (the stage pass times the stages ONE AFTER THE OTHER.  In the timed region the in-cell ranking -- most of post_copy -- runs on
+                # a stream of its own next to cond_cellfinish, sync_out, hskpng_Tpr and hskpng_vterm_all, so the stages add up to more than
+                # ms_per_step)
+                "stage_note": "stages timed serially by the stage pass; in the timed region post_copy's in-cell ranking overlaps cond_cellfinish .. hskpng_vterm_all",
+                "stage_roofline": stage_roof,
+            })
         if spmd or native_multi:
             # what ran, for a reader of an N-GPU record: how many ranks did work, how the migrants travelled, how often a message needed
             # its second part
@@ -761,7 +804,7 @@ def main():
             coal_stress["reorder_storage_ms"] = out["stage_ms_per_step"].get("reorder_storage")
             coal_stress["post_copy_ms"] = out["stage_ms_per_step"].get("post_copy")
             out["coal_stress"] = coal_stress
-        legs_ok = world_out == 1 and args.cond_mode == "percell" and not args.self_ring
+        legs_ok = args.full and world_out == 1 and args.cond_mode == "percell" and not args.self_ring
         if legs_ok:
             # Further SHORT measurements on the same box, each on an object of its own built from the headline's options with one thing
             # changed.  The headline object goes first (its two attribute sets and housekeeping are tens of GB), and every leg gets
@@ -921,7 +964,7 @@ def main():
                     out["c5"]["workload"] = "3-D box %dx%dx%d cells x 512 SD/cell (BASELINE configs[4]), headline options" % (nx_tot, ny, nz)
                 else:
                     out["c5"] = {"skipped": "%.0f GB of device memory free, the configuration needs ~210" % (free_b / 1e9)}
-        if world_out == 1 and not args.no_cpu_baseline and not args.self_ring:
+        if args.full and world_out == 1 and not args.no_cpu_baseline and not args.self_ring:
             out["cpu_baseline"] = cpu_baseline(args)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

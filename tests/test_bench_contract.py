@@ -1,5 +1,5 @@
-"""bench.py's contract with the driver: ONE JSON line on stdout with the agreed keys (the roofline and cpu_baseline objects included),
-and the host-side helpers of its CPU leg.  The GPU test runs the real script on a small box."""
+"""bench.py's contract with the driver: ONE JSON line on stdout with the agreed keys (with --full: the roofline and cpu_baseline objects
+included), --dump-outputs, and the host-side helpers of its CPU leg.  The GPU tests run the real script on a small box."""
 import json
 import os
 import subprocess
@@ -12,8 +12,12 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-            "data", "config", "roofline")
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+            "data", "config")
+REQUIRED = HEADLINE + ("roofline",)
+# what only --full measures
+FULL_ONLY = ("roofline", "stage_ms_per_step", "stage_roofline", "cpu_baseline", "strict_fp", "api_default", "host_arrays", "coal_stress", "c2",
+             "c5", "soak", "activation")
 
 
 def test_cpu_baseline_leg_on_a_small_sample():
@@ -25,6 +29,28 @@ def test_cpu_baseline_leg_on_a_small_sample():
     assert r["kind"] == "port" and r["unit"] == "super-droplets/s" and r["value"] > 0
     assert 1 <= r["cores"] <= (os.cpu_count() or 1) and r["cores"] <= r["cpu_quota"]
     assert "6^3" in r["sample"]
+
+
+def test_dump_outputs_writes_whole_arrays_within_the_budget_and_a_fixed_sample_beyond_it(tmp_path, monkeypatch):
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"th": rng.random((8, 4, 4)), "rv": rng.random((8, 4, 4)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for nm, a in arrays.items():
+        got = np.load(tmp_path / "whole" / (nm + ".npy"))
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 600)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = 0
+    for nm, a in arrays.items():
+        got, again = np.load(tmp_path / "a" / (nm + ".npy")), np.load(tmp_path / "b" / (nm + ".npy"))
+        assert np.array_equal(got, again) and got.dtype == a.dtype and 0 < got.size < a.size
+        assert np.isin(got, a).all() and np.all(np.diff(np.flatnonzero(np.isin(a.reshape(-1), got))) > 0)
+        total += got.nbytes
+    assert total <= 600
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "c"), {"n": np.arange(4)})
 
 
 def test_cpu_quota_is_a_positive_count_within_the_affinity_mask():
@@ -47,8 +73,8 @@ def test_synthetic_fields_have_the_shapes_the_api_wants():
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--self-ring"]])
 def test_bench_prints_one_json_line_with_the_agreed_keys(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "16", "--steps", "4", "--warmup", "1", "--cpu-sample-n", "6", "--cpu-sample-steps", "1",
-           "--strict-leg-steps", "2", "--leg-steps", "2", "--stage-steps", "2"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "16", "--steps", "4", "--warmup", "1", "--cpu-sample-n", "6",
+           "--cpu-sample-steps", "1", "--strict-leg-steps", "2", "--leg-steps", "2", "--stage-steps", "2"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.split("\n") if l.strip()]
@@ -77,9 +103,42 @@ def test_bench_prints_one_json_line_with_the_agreed_keys(extra):
 
 
 @pytest.mark.gpu
+def test_plain_bench_prints_only_the_headline_and_dumps_the_last_steps_fields(tmp_path):
+    """a plain run (no --full) times --steps steps and prints the headline keys, nothing that takes runs of its own; --dump-outputs
+    writes the caller's th and rv after the last timed step, the same from run to run"""
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "16", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.split("\n") if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for k in HEADLINE:
+            assert k in d, k
+        for k in FULL_ONLY:
+            assert k not in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / d["config"]["super_droplets"] - 1) < 0.05
+        dumps.append({nm: np.load(tmp_path / run / (nm + ".npy")) for nm in ("th", "rv")})
+    th0, rv0 = bench_fields_at_start(16)
+    for nm, start in (("th", th0), ("rv", rv0)):
+        a, b = dumps[0][nm], dumps[1][nm]
+        assert a.shape == (16, 16, 16) and a.dtype == np.float64 and np.isfinite(a).all()
+        np.testing.assert_allclose(a, b, rtol=1e-9)
+        assert not np.array_equal(a, start)                # (the steps changed the caller's fields in place)
+
+
+def bench_fields_at_start(n):
+    import bench
+    th, rv = bench.make_fields(n, n, n, 0, n, np, np.float64)[:2]
+    return np.broadcast_to(th, (n, n, n)), np.broadcast_to(rv, (n, n, n))
+
+
+@pytest.mark.gpu
 def test_bench_coal_stress_workload_reports_collisions():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "coal-stress", "--n", "16", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-           "--no-strict-leg", "--no-toms-leg", "--no-host-leg", "--stage-steps", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "coal-stress", "--n", "16", "--steps", "4", "--warmup", "2",
+           "--no-cpu-baseline", "--no-strict-leg", "--no-toms-leg", "--no-host-leg", "--stage-steps", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.split("\n") if l.strip()][0])

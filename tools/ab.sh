@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/ab.sh <tag> <other.so> [bench args]'  ->  gpurun_out/ab_<tag>/{new,old}.json
 tag=$1; other=$2; shift 2
 out=gpurun_out/ab_$tag; mkdir -p $out
-B="python3 bench.py --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --steps 100 $*"
+B="python3 bench.py --full --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --steps 100 $*"
 so=libcloudphxx_amd/csrc/liblcx_hip.so
 $B > $out/new.json 2> $out/new.err
 cp $so $out/../_new.so; cp tools/_ab/$other $so

@@ -5,7 +5,7 @@
 # the chip prices a launch in lanes that compute, not in instructions that issue (the condensation kernel).
 tag=${1:-x}; shift
 out=gpurun_out/power_$tag; mkdir -p $out
-B="python3 bench.py --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --no-extra-legs --steps 1500 --stage-steps 0 $*"
+B="python3 bench.py --full --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --no-extra-legs --steps 1500 --stage-steps 0 $*"
 ( for i in $(seq 1 400); do /opt/rocm/bin/rocm-smi --showpower --showclocks --showtemp --json 2>/dev/null | head -c 4000; echo; sleep 0.15; done ) > $out/smi.log 2>&1 &
 SMI=$!
 $B > $out/bench.json 2> $out/bench.err

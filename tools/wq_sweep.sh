@@ -4,7 +4,7 @@
 # a variant = comma-separated opts_init.dbg_flags names / budget=N (bench.py --dbg), or `default`
 tag=$1; shift
 out=gpurun_out/wq_$tag; mkdir -p $out
-B="python3 bench.py --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --no-extra-legs --steps ${STEPS:-60} --warmup ${WARMUP:-20} $BENCH_ARGS"
+B="python3 bench.py --full --no-cpu-baseline --no-strict-leg --no-toms-leg --no-host-leg --no-extra-legs --steps ${STEPS:-60} --warmup ${WARMUP:-20} $BENCH_ARGS"
 vars="$@"
 [ -z "$vars" ] && vars="default COND_BUDGET COND_BUDGET,budget=1 COND_BUDGET,budget=3 COND_WQ default"
 i=0
