@@ -71,9 +71,10 @@ typedef struct {
 typedef struct { double kappa, rd_insol, radius, conc; int sd_count; } lcx_dry_size_t;
 
 /* POD mirror of opts_init_t<real_t> (opts_init.hpp:29-253); same field names and defaults.
- * Fields of sub-systems that are out of scope (chemistry, ice, sources, relaxation, SGS
- * turbulence) are kept so that a caller's settings are checked, not silently dropped:
- * lcx_create() fails if one of them is switched on. */
+ * Fields of sub-systems that are out of scope (chemistry, ice, relaxation) are kept so that a
+ * caller's settings are checked, not silently dropped: lcx_create() fails if one of them is
+ * switched on.  The aerosol source (src_type simple / matching, the box src_x0 .. src_z1 here,
+ * the spectra in lcx_opts_t) is built. */
 typedef struct {
   int nx, ny, nz;
   double dx, dy, dz, dt;
@@ -150,6 +151,9 @@ typedef struct {
                          * The lean solver's folded kernel (k_cond_lean_fold): > 0 = slots of its LDS stage in use (at most 128; a test makes it
                          * small so that unconverged droplets stay in their own lanes) */
   int dbg_pack_delay_us;/* multi-device tests: slabs with an odd first plane send their messages so many microseconds late */
+  /* box in which the aerosol source creates super-droplets (opts_init.hpp: src_x0 .. src_z1, default 0; src_type above:
+   * 0 off, 1 simple, 2 matching, ccn_source.hpp).  src_x0 == src_x1 == 0 switches the source of this domain off. */
+  double src_x0, src_y0, src_z0, src_x1, src_y1, src_z1;
 } lcx_opts_init_t;
 
 enum lcx_dbg {
@@ -215,12 +219,21 @@ enum lcx_cond_kernel {
   LCX_CK_SUBSTEPS = 13                 /* k_cond_substeps: fast arithmetic, sstp_cond > 1 -- every substep of the step in one launch */
 };
 
+/* one entry of src_dry_distros_t (opts.hpp): spectrum of the source PER SECOND, number of super-droplets (= size bins) it adds per
+ * cell of the source box, and the number of steps between two firings */
+typedef struct { lcx_distro_t distro; unsigned long long sd_conc; int supstp; } lcx_src_distro_t;
+/* one (kappa, rd_insol, radius) -> (STP concentration per second, SD count, supstp) entry of src_dry_sizes_t */
+typedef struct { double kappa, rd_insol, radius, conc_per_s; int sd_count, supstp; } lcx_src_size_t;
+
 /* POD mirror of opts_t<real_t> (opts.hpp:20-50) */
 typedef struct {
   int adve, sedi, subs, cond, coal, src, rlx, rcyc, turb_adve, turb_cond, turb_coal, ice_nucl;
   int chem_dsl, chem_dsc, chem_rct;
   double RH_max;
   double dt;
+  /* aerosol source (used when src != 0); the arrays need only live for the duration of the lcx_step_async call */
+  const lcx_src_distro_t *src_dry_distros; int n_src_dry_distros;   /* sorted by (kappa, rd_insol) like std::map */
+  const lcx_src_size_t *src_dry_sizes; int n_src_dry_sizes;         /* sorted by (kappa, rd_insol, radius) */
 } lcx_opts_t;
 
 /* arrinfo_t (arrinfo.hpp:11-49): data == NULL <=> "not provided".  strides in elements.

@@ -1,4 +1,4 @@
-#pragma once   // reference lgrngn/ccn_source.hpp:8 (sources are outside the accelerated path: only `off` is accepted); src_name: ccn_source.hpp:14-18
+#pragma once   // reference lgrngn/ccn_source.hpp:8 (opts_init.src_type: off, or new super-droplets in the box src_x0 .. src_z1 -- simple: always created, matching: added to existing ones of like size); src_name: ccn_source.hpp:14-18
 #include "enum_names.hpp"
 namespace libcloudphxx { namespace lgrngn {
   enum class src_t { off, simple, matching };

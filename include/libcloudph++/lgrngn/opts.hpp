@@ -10,7 +10,7 @@ namespace libcloudphxx { namespace lgrngn {
     real_t RH_max = 44;                         // anything above 1.1 means "no limit"
     bool chem_dsl = false, chem_dsc = false, chem_rct = false;
     real_t dt = -1;                             // < 0: use opts_init.dt
-    src_dry_distros_t<real_t> src_dry_distros;  // aerosol sources: not part of the accelerated path
+    src_dry_distros_t<real_t> src_dry_distros;  // aerosol source (opts_init.src_type): spectrum per second, SDs per cell, steps between firings
     src_dry_sizes_t<real_t> src_dry_sizes;
   };
 } }

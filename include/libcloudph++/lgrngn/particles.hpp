@@ -143,6 +143,7 @@ namespace libcloudphxx { namespace lgrngn {
       c.n_x_tot = n_x_tot; c.strict_fp = o.strict_fp; c.cond_solver = o.cond_solver; c.reorder_every = o.reorder_every; c.stream_ordered = o.stream_ordered;
       c.dbg_flags = o.dbg_flags;
       c.n_x_bfr = o.n_x_bfr; c.bcond_lft = o.bcond_lft; c.bcond_rgt = o.bcond_rgt;
+      c.src_x0 = o.src_x0; c.src_y0 = o.src_y0; c.src_z0 = o.src_z0; c.src_x1 = o.src_x1; c.src_y1 = o.src_y1; c.src_z1 = o.src_z1;
       // std::map iterates in (kappa, rd_insol) order, which is the order the library expects
       std::vector<lcx_distro_t> dd;
       for (const auto &kv : pimpl->opts_init.dry_distros) {
@@ -189,8 +190,22 @@ namespace libcloudphxx { namespace lgrngn {
     }
     void step_async(const opts_t<real_t> &opts) override
     {
-      if (!opts.src_dry_distros.empty() || !opts.src_dry_sizes.empty()) throw std::runtime_error("libcloudph++: aerosol source was switched off in opts_init");
-      const lcx_opts_t oc = conv(opts);
+      lcx_opts_t oc = conv(opts);
+      // the aerosol source's spectra: arrays in std::map order that live until the call returns
+      std::vector<lcx_src_distro_t> sd;
+      for (const auto &kv : opts.src_dry_distros) {
+        lcx_src_distro_t e{};
+        e.distro.kappa = kv.first.kappa; e.distro.rd_insol = kv.first.rd_insol;
+        e.distro.fn = &detail::distro_trampoline<real_t>; e.distro.user = std::get<0>(kv.second).get();
+        e.sd_conc = (unsigned long long)(std::get<1>(kv.second)); e.supstp = std::get<2>(kv.second);
+        sd.push_back(e);
+      }
+      std::vector<lcx_src_size_t> ss;
+      for (const auto &kv : opts.src_dry_sizes) for (const auto &rc : kv.second)
+        ss.push_back(lcx_src_size_t{double(kv.first.kappa), double(kv.first.rd_insol), double(rc.first), double(std::get<0>(rc.second)),
+                                    std::get<1>(rc.second), std::get<2>(rc.second)});
+      oc.src_dry_distros = sd.empty() ? nullptr : sd.data(); oc.n_src_dry_distros = int(sd.size());
+      oc.src_dry_sizes = ss.empty() ? nullptr : ss.data(); oc.n_src_dry_sizes = int(ss.size());
       detail::lcx_check(lcx_step_async(pimpl->h, &oc));
     }
 

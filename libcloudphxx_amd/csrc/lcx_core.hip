@@ -254,8 +254,9 @@ struct Particles : IParticles {
   // ------------------------------------------------------------------------------------------
   explicit Particles(const lcx_opts_init_t &oi) : o(oi)
   {
-    if (oi.chem_switch || oi.ice_switch || oi.rlx_switch || oi.src_type)
-      throw lcx_error("libcloudph++: option outside the accelerated hot path (chem/ice/src/rlx)");
+    if (oi.chem_switch || oi.ice_switch || oi.rlx_switch)
+      throw lcx_error("libcloudph++: option outside the accelerated hot path (chem/ice/rlx)");
+    if (oi.src_type < 0 || oi.src_type > 2) throw lcx_error("libcloudph++: unknown opts_init.src_type");
     if (oi.n_sd_max >= (1ull << 32)) throw lcx_error("libcloudph++: n_sd_max must be < 2^32 per device (32-bit super-droplet ids)");
     distros.assign(oi.dry_distros, oi.dry_distros + oi.n_dry_distros);
     sizes.assign(oi.dry_sizes, oi.dry_sizes + oi.n_dry_sizes);
@@ -320,6 +321,7 @@ struct Particles : IParticles {
     puddle_partial.alloc(size_t(nblk(cap)) * 4); puddle_sum.alloc(4 + 256 * 4); puddle_acc.alloc_zero(4, st);
     outbuf_h.assign(ncell, T(0));
     if (distmem()) alloc_mig();
+    if (o.src_type && n_dims >= 2) list_src_cells();
   }
   ~Particles() override
   {
@@ -1551,12 +1553,13 @@ struct Particles : IParticles {
       }
     }
     else hipLaunchKernelGGL((k_move<T, false, false>), dim3(blocks), dim3(BS), 0, st, a);
-    if (reindex && !distmem()) list_big_from_hist();                    // (with neighbours: after their immigrants are in, exch_unpack)
+    if (reindex && !distmem() && !hold_big_list) list_big_from_hist();  // (with neighbours: after their immigrants are in, exch_unpack;
+                                                                        // hold_big_list: after the aerosol source's newcomers are in, step_async)
     if (want_puddle && dev_exchange) puddle_pending_blocks = blocks;      // (reduced after the emigrants are on their way, see lcx_multi.hpp)
     else if (want_puddle) puddle_reduce(blocks);
     if (do_bcnd && distmem()) build_migrant_lists();
   }
-  unsigned puddle_pending_blocks = 0;
+  unsigned puddle_pending_blocks = 0; bool hold_big_list = false;
   void puddle_reduce_deferred() { if (puddle_pending_blocks) puddle_reduce(puddle_pending_blocks); puddle_pending_blocks = 0; }
   void puddle_reduce(unsigned blocks)
   {
@@ -1596,18 +1599,19 @@ struct Particles : IParticles {
       res += d.n_stp[m] / std::sqrt(2 * M_PI) / std::log(d.sdev[m]) * std::exp(-std::pow((lnrd - std::log(d.mean_rd[m])), 2) / 2. / std::pow(std::log(d.sdev[m]), 2));
     return res;
   }
-  void init_dist_analysis_sd_conc(const lcx_distro_t &d, n_t sd_conc, T dv0)
+  // dt_: 1 at initialisation; the aerosol source's spectrum is per second and the entry stands for supstp * dt seconds of it
+  void init_dist_analysis_sd_conc(const lcx_distro_t &d, n_t sd_conc, T dv0, T dt_ = T(1))
   {                                                                                      // init_dist_analysis.ipp:17-77
     const T vol = n_dims == 0 ? dv0 : T(T(o.dx) * T(o.dy) * T(o.dz));
     if (o.rd_min >= 0 && o.rd_max >= 0) {
       const T rd_min = T(o.rd_min), rd_max = T(o.rd_max);
-      multiplier = T(std::log(rd_max / rd_min) / sd_conc * T(1) * vol);
+      multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
       log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
     } else if (o.rd_min < 0 && o.rd_max < 0) {
       T rd_min = T(1e-14), rd_max = T(1e-3);                                             // config.hpp:23-24
       bool found = false;
       while (!found) {
-        multiplier = T(std::log(rd_max / rd_min) / sd_conc * T(1) * vol);
+        multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
         log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
         const n_t n_min = n_t(T(eval_distro(d, log_rd_min)) * T(multiplier)), n_max = n_t(T(eval_distro(d, log_rd_max)) * T(multiplier));
         if (rd_min == T(1e-14) && n_min != 0) throw lcx_error("Initial dry radii distribution is non-zero (" + std::to_string(n_min) + ") for rd_min_init (1e-14)");
@@ -1758,24 +1762,7 @@ struct Particles : IParticles {
       lognormal_modes lm{d.n_modes, {0}, {0}, {0}};
       for (int m = 0; m < 4; ++m) { lm.mean_rd[m] = d.mean_rd[m]; lm.sdev[m] = d.sdev[m]; lm.n_stp[m] = d.n_stp[m]; }
       const T *fv = nullptr;
-      if (d.fn) {                                                                        // host evaluation of the user functor (init_n.ipp:56-84)
-        // The host evaluates n(ln rd) -- and, since round 4, the dry volume rd3 = exp(3 ln rd) that the reference takes ln rd back from
-        // (init_dry_sd_conc.ipp:26-34, init_n.ipp:62-66): with the host's exp and log on both sides of that round trip the argument of
-        // the user's function, hence the integer multiplicity, is the reference's bit for bit (the device's exp differs from the
-        // host's in the last place now and then, which used to move n by one for < 0.1 % of the super-droplets)
-        std::vector<T> h(n_new), r3(n_new);
-        HIPCHK(hipMemcpyAsync(h.data(), fvals.p, n_new * sizeof(T), hipMemcpyDeviceToHost, st));      // (the drawn ln rd)
-        sync();
-        for (size_t i = 0; i < n_new; ++i) {
-          r3[i] = T(std::exp(3 * h[i]));
-          const T lnrd = T(std::log(r3[i]) / 3.);
-          h[i] = T(d.fn(lnrd, d.user));
-        }
-        HIPCHK(hipMemcpyAsync(A.rd3.p + n_old, r3.data(), n_new * sizeof(T), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(fvals.p, h.data(), n_new * sizeof(T), hipMemcpyHostToDevice, st));
-        sync();
-        fv = fvals.p;
-      }
+      if (d.fn) { eval_fn_on_host(d, n_new, n_old); fv = fvals.p; }
       hipLaunchKernelGGL(k_init_n<T>, dim3(nb), dim3(BS), 0, st, n_new, n_old, A.rd3.p, ijk.p, fv, lm, T(multiplier), rhod.p, dv.p,
                          conc_factor_h.empty() ? (const T *)nullptr : conc_factor.p, m1(o.nz), o.aerosol_independent_of_rhod, n_dims,
                          T(T(o.dx) * T(o.dy) * T(o.dz)), A.n.p);
@@ -1790,6 +1777,25 @@ struct Particles : IParticles {
       }
     }
     release_replay_keep();
+  }
+  // host evaluation of the user functor (init_n.ipp:56-84) for the n_new super-droplets behind n_old; fvals holds their drawn ln rd
+  void eval_fn_on_host(const lcx_distro_t &d, size_t n_new, size_t n_old)
+  {
+    // The host evaluates n(ln rd) -- and, since round 4, the dry volume rd3 = exp(3 ln rd) that the reference takes ln rd back from
+    // (init_dry_sd_conc.ipp:26-34, init_n.ipp:62-66): with the host's exp and log on both sides of that round trip the argument of
+    // the user's function, hence the integer multiplicity, is the reference's bit for bit (the device's exp differs from the
+    // host's in the last place now and then, which used to move n by one for < 0.1 % of the super-droplets)
+    std::vector<T> h(n_new), r3(n_new);
+    HIPCHK(hipMemcpyAsync(h.data(), fvals.p, n_new * sizeof(T), hipMemcpyDeviceToHost, st));      // (the drawn ln rd)
+    sync();
+    for (size_t i = 0; i < n_new; ++i) {
+      r3[i] = T(std::exp(3 * h[i]));
+      const T lnrd = T(std::log(r3[i]) / 3.);
+      h[i] = T(d.fn(lnrd, d.user));
+    }
+    HIPCHK(hipMemcpyAsync(A.rd3.p + n_old, r3.data(), n_new * sizeof(T), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fvals.p, h.data(), n_new * sizeof(T), hipMemcpyHostToDevice, st));
+    sync();
   }
   void init_positions(size_t n_new, size_t n_old)
   {                                                                                      // init_xyz.ipp:40-74
@@ -1816,6 +1822,135 @@ struct Particles : IParticles {
       hipLaunchKernelGGL(k_init_wet<T>, dim3(nblk(n_new)), dim3(BS), 0, st, n_new, n_old, A.rd3.p, A.kpa.p, ijk.p, RH.p, Tk.p, T(o.RH_max), A.rw2.p);
       init_positions(n_new, n_old);
     }
+    release_replay_keep();
+  }
+  // ------------------------------------------------------------------------------------------
+  // aerosol source (particles_step.ipp:448-479, src/impl/sources_and_relaxation_of_SDs/): opts_init.src_type simple / matching,
+  // spectra and sizes in opts_t.  The source is built from the initialisation's own kernels: they append `n_new` super-droplets behind
+  // `n_old`, here with the cells of the source box (src_cells) in the place of "every cell".
+  // ------------------------------------------------------------------------------------------
+  std::vector<uint32_t> src_cells_h; DevBuf<uint32_t> src_cells;
+  size_t src_stp_ctr = 0, tag_next = 0;      // tag_next: LCX_DBG_TAG, the tag of the next super-droplet that a source creates
+  bool src_box_on() const { return !(o.src_x0 == 0 && o.src_x1 == 0); }      // (how a slab without source is marked, distmem_opts.hpp:35-39)
+  void list_src_cells()
+  {                                                                                      // init_count_num.ipp:120-175
+    auto edge = [](double v, double d, int n) { const double e = v / d + 0.5; return e <= 0 ? size_t(0) : std::min(size_t(e), size_t(n)); };
+    const size_t i0 = edge(o.src_x0, o.dx, o.nx), i1 = edge(o.src_x1, o.dx, o.nx), k0 = edge(o.src_z0, o.dz, o.nz), k1 = edge(o.src_z1, o.dz, o.nz);
+    const size_t j0 = n_dims == 3 ? edge(o.src_y0, o.dy, o.ny) : 0, j1 = n_dims == 3 ? edge(o.src_y1, o.dy, o.ny) : 1;
+    for (size_t i = i0; i < i1; ++i) for (size_t j = j0; j < j1; ++j) for (size_t k = k0; k < k1; ++k)
+      src_cells_h.push_back(uint32_t((i * size_t(m1(o.ny)) + j) * size_t(o.nz) + k));
+    src_cells.alloc(src_cells_h.size());
+    h2d(src_cells.p, src_cells_h.data(), src_cells_h.size() * sizeof(uint32_t));
+  }
+  static bool src_fires(size_t ctr, int supstp)
+  {
+    if (supstp <= 0) throw lcx_error("libcloudph++: supstp of an aerosol source entry must be greater than 0");
+    return ctr % size_t(supstp) == 0;
+  }
+  // the errors that src_dry_distros.ipp:19-23 raises whenever the source is called, and whether any entry fires in this step
+  bool src_check_and_fires(const lcx_opts_t &opts) const
+  {
+    if (opts.n_src_dry_distros > 1) throw lcx_error("libcloudph++: src_dry_distros can only have a single kappa value.");
+    if (o.src_type == 2 && opts.n_src_dry_distros && (distros.empty() || opts.src_dry_distros[0].distro.kappa != distros[0].kappa))
+      throw lcx_error("libcloudph++: For 'matching' CCN source, kappa of the source has to be the same as that of the initial profile (no kappa matching done)");
+    bool any = false;
+    for (int i = 0; i < opts.n_src_dry_distros; ++i) any |= src_fires(src_stp_ctr, opts.src_dry_distros[i].supstp);
+    for (int i = 0; i < opts.n_src_dry_sizes; ++i) any |= src_fires(src_stp_ctr, opts.src_dry_sizes[i].supstp);
+    return any && !src_cells_h.empty();
+  }
+  // super-droplets (candidates, for matching) that this step's firing entries append
+  size_t src_total_new(const lcx_opts_t &opts) const
+  {
+    size_t per_cell = 0;
+    for (int i = 0; i < opts.n_src_dry_distros; ++i) if (src_fires(src_stp_ctr, opts.src_dry_distros[i].supstp)) per_cell += size_t(opts.src_dry_distros[i].sd_conc);
+    for (int i = 0; i < opts.n_src_dry_sizes; ++i) if (src_fires(src_stp_ctr, opts.src_dry_sizes[i].supstp)) per_cell += size_t(opts.src_dry_sizes[i].sd_count);
+    return per_cell * src_cells_h.size();
+  }
+  // room for n_new more super-droplets behind the storage extent; returns where they begin (plain sequence only: compacting would
+  // void the histogram of a fused move, so a step that is short of room does not take the fused move, step_async)
+  size_t src_make_room(size_t n_new)
+  {
+    if (nphys + n_new > cap && !distmem()) {       // dead super-droplets not yet compacted away may be in the way
+      lcx_opts_t od; lcx_opts_default(&od);
+      post_copy(od, true);
+    }
+    check_npart(nphys + n_new);
+    return nphys;
+  }
+  // what every new super-droplet gets whatever it was drawn from: wet radius, position, the extension attributes
+  void src_finish_new(size_t n_new, size_t n_old, T kappa)
+  {
+    hipLaunchKernelGGL(k_init_wet<T>, dim3(nblk(n_new)), dim3(BS), 0, st, n_new, n_old, A.rd3.p, A.kpa.p, ijk.p, RH.p, Tk.p, T(o.RH_max), A.rw2.p);
+    init_positions(n_new, n_old);
+    for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0) HIPCHK(hipMemsetAsync(A.ext[ix].p + n_old, 0, n_new * sizeof(T), st));
+    if (ix_rc2 >= 0) hipLaunchKernelGGL(k_fill<T>, dim3(nblk(n_new)), dim3(BS), 0, st, A.ext[ix_rc2].p + n_old, n_new, T(-1));
+    if (ix_tag >= 0) hipLaunchKernelGGL(k_fill_index_from<T>, dim3(nblk(n_new)), dim3(BS), 0, st, A.ext[ix_tag].p + n_old, n_new, T(tag_next));
+    tag_next += n_new;
+    nphys = n_old + n_new;
+    zero_n_unmarked = true;                          // (a multiplicity may round to zero; matching clears those it hands on)
+    if (kpa_uniform && kappa != kpa_value) kpa_uniform = false;
+  }
+  void src_dry_distro(const lcx_src_distro_t &e)
+  {                                                                                      // src_dry_distros_simple.ipp:19-88, _matching.ipp:50-417
+    const lcx_distro_t &d = e.distro;
+    const n_t per_cell = e.sd_conc;
+    const size_t n_new = size_t(per_cell) * src_cells_h.size();
+    if (n_new == 0) return;
+    const bool matching = o.src_type == 2;
+    if (matching && per_cell > n_t(SRC_MATCH_MAX_BINS))
+      throw lcx_error("libcloudph++ (HIP): src_type matching supports up to " + std::to_string(SRC_MATCH_MAX_BINS) + " super-droplets (size bins) per cell in src_dry_distros");
+    init_dist_analysis_sd_conc(d, per_cell, T(0), T(T(e.supstp) * T(o.dt)));
+    if (log_rd_min >= log_rd_max) throw lcx_error("Distribution analysis error: rd_min >= rd_max");
+    if (matching && distmem())
+      throw lcx_error("libcloudph++ (HIP): src_type matching is not available on a decomposed domain (a slab with neighbours); use src_type simple there");
+    if (matching) {
+      // matching walks the old super-droplets cell by cell: the cell-sorted order of the positions the move has just left (one
+      // post_copy-like pass of its own; the one at the end of the step counts the newcomers in)
+      lcx_opts_t od; lcx_opts_default(&od);
+      post_copy(od);
+    }
+    const size_t n_old = src_make_room(n_new);
+    const unsigned nb = nblk(n_new);
+    {
+      const u01_src<T> rs = rand_u01(n_new);
+      if (d.fn) fvals.alloc(n_new);
+      hipLaunchKernelGGL(k_init_dry<T>, dim3(nb), dim3(BS), 0, st, n_new, n_old, per_cell, T(log_rd_min), T(log_rd_max), rs, ijk.p, A.rd3.p, A.kpa.p, T(d.kappa), A.vt.p,
+                         d.fn ? fvals.p : (T *)nullptr, (const uint32_t *)src_cells.p);
+    }
+    lognormal_modes lm{d.n_modes, {0}, {0}, {0}};
+    for (int m = 0; m < 4; ++m) { lm.mean_rd[m] = d.mean_rd[m]; lm.sdev[m] = d.sdev[m]; lm.n_stp[m] = d.n_stp[m]; }
+    const T *fv = nullptr;
+    if (d.fn) { eval_fn_on_host(d, n_new, n_old); fv = fvals.p; }       // a user's function is evaluated on the host, as at initialisation
+    hipLaunchKernelGGL(k_init_n<T>, dim3(nb), dim3(BS), 0, st, n_new, n_old, A.rd3.p, ijk.p, fv, lm, T(multiplier), rhod.p, dv.p,
+                       conc_factor_h.empty() ? (const T *)nullptr : conc_factor.p, m1(o.nz), o.aerosol_independent_of_rhod, n_dims,
+                       T(T(o.dx) * T(o.dy) * T(o.dz)), A.n.p);
+    if (matching && npart) {
+      // candidates whose size bin is taken in their cell hand their multiplicity to an old super-droplet and are left with n = 0: no
+      // count comes back to the host, post_copy drops them with the step's other dead super-droplets (k_src_match)
+      const uint64_t call = ++rng_call, seed = uint64_t(uint32_t(seed_now()));
+      hipLaunchKernelGGL(k_src_match<T>, dim3(unsigned(src_cells_h.size())), dim3(BS), size_t(per_cell) * sizeof(unsigned long long), st,
+                         (const uint32_t *)src_cells.p, uint32_t(per_cell), T(log_rd_min), T(log_rd_max), (const uint32_t *)cell_start.p, (const uint32_t *)sid(),
+                         (const T *)A.rd3.p, A.n.p, n_old, call, seed);
+    }
+    src_finish_new(n_new, n_old, T(d.kappa));
+  }
+  void src_dry_size(const lcx_src_size_t &e)
+  {                                                                                      // src_dry_sizes.ipp:15-100
+    const n_t per_cell = n_t(e.sd_count);
+    const size_t n_new = size_t(per_cell) * src_cells_h.size();
+    if (n_new == 0) return;
+    const size_t n_old = src_make_room(n_new);
+    const T r = T(e.radius), sup_dt = T(T(e.supstp) * T(o.dt));
+    hipLaunchKernelGGL(k_init_sizes<T>, dim3(nblk(n_new)), dim3(BS), 0, st, n_new, n_old, per_cell, T(r * r * r), T(e.kappa), T(T(e.conc_per_s) * sup_dt), dv.p, rhod.p,
+                       conc_factor_h.empty() ? (const T *)nullptr : conc_factor.p, m1(o.nz), o.aerosol_independent_of_rhod, ijk.p, A.rd3.p, A.kpa.p, A.vt.p, A.n.p,
+                       (const uint32_t *)src_cells.p);
+    src_finish_new(n_new, n_old, T(e.kappa));
+  }
+  void src(const lcx_opts_t &opts)
+  {                                                                                      // src.ipp:13-24
+    Range r(this, "src");
+    for (int i = 0; i < opts.n_src_dry_distros; ++i) if (src_fires(src_stp_ctr, opts.src_dry_distros[i].supstp)) src_dry_distro(opts.src_dry_distros[i]);
+    for (int i = 0; i < opts.n_src_dry_sizes; ++i) if (src_fires(src_stp_ctr, opts.src_dry_sizes[i].supstp)) src_dry_size(opts.src_dry_sizes[i]);
     release_replay_keep();
   }
   void init_kernel()
@@ -1860,6 +1995,12 @@ struct Particles : IParticles {
       if (!(o.y1 > o.y0 && o.y1 <= m1(o.ny) * o.dy)) throw lcx_error("libcloudph++: !(y1 > y0 & y1 <= min(1,ny)*dy)");
       if (!(o.z1 > o.z0 && o.z1 <= m1(o.nz) * o.dz)) throw lcx_error("libcloudph++: !(z1 > z0 & z1 <= min(1,nz)*dz)");
     }
+    if (o.src_type == 2 && distros.size() > 1)
+      throw lcx_error("libcloudph++: For 'matching' CCN source, the initial aerosol distribution can only have one kappa value (na kappa matching done).");
+    if (o.src_type != 0 && n_dims < 2) throw lcx_error("libcloudph++: CCN source works in 2D and 3D only.");
+    if (o.sd_const_multi > 0 && o.src_type != 0) throw lcx_error("libcloudph++: aerosol source and constant multiplicity option are not compatible");
+    if (o.src_type != 0 && o.exact_sstp_cond)
+      throw lcx_error("libcloudph++ (HIP): aerosol source and per-particle condensation substepping (opts_init.exact_sstp_cond) are not compatible");
     if (o.dt == 0) throw lcx_error("libcloudph++: please specify opts_init.dt");
     if (o.sd_conc * o.sd_const_multi != 0) throw lcx_error("libcloudph++: specify either opts_init.sd_conc or opts_init.sd_const_multi, not both");
     if (o.sd_conc == 0 && o.sd_const_multi == 0 && o.n_dry_sizes == 0) throw lcx_error("libcloudph++: please specify opts_init.sd_conc, opts_init.sd_const_multi or opts_init.dry_sizes");
@@ -1931,6 +2072,7 @@ struct Particles : IParticles {
       hipLaunchKernelGGL(k_init_vt0<T>, dim3(nblk(size_t(vtc.n_bin))), dim3(BS), 0, st, vt_0.p, vtc);
     }
     if (ix_tag >= 0 && nphys) hipLaunchKernelGGL(k_fill_index<T>, dim3(nblk(nphys)), dim3(BS), 0, st, A.ext[ix_tag].p, nphys);
+    tag_next = nphys;
     hskpng_vterm(true);
     hskpng_approximate_rc2_invalid();                                                    // particles_init.ipp:116-117
     sstp_save();
@@ -2012,12 +2154,19 @@ struct Particles : IParticles {
     if (opts.turb_adve && !o.turb_adve_switch) throw lcx_error("libcloudph++: turb_adve_switch=False, but turb_adve==True");
     if (opts.turb_coal && !o.turb_coal_switch) throw lcx_error("libcloudph++: turb_coal_switch=False, but turb_coal==True");   // the reference reads an empty diss_rate here
     if (opts.turb_adve && n_dims == 0) throw lcx_error("libcloudph++: turbulent advection does not work in 0D");
-    if (opts.src) throw lcx_error("libcloudph++: aerosol source was switched off in opts_init");
+    if (opts.src && o.src_type == 0) throw lcx_error("libcloudph++: aerosol source was switched off in opts_init");
+    // A step in which no source entry fires launches what it launches without a source.  One in which an entry fires appends behind
+    // the move.  simple / dry_sizes on a single device keep the fused move: the newcomers are put into the histogram that the move has
+    // left (as migrate_unpack does with immigrants), so the step ends like any other -- deferred sort and all -- and the host waits no
+    // more often than without a source.  matching, which needs the cell-sorted order in the middle of the step, and a slab with
+    // neighbours take the plain sequence (move, append, post_copy), as a step with opts.rcyc does.
+    const bool src_now = opts.src && src_box_on() && src_check_and_fires(opts);
+    const bool src_plain = src_now && (o.src_type == 2 || distmem() || nphys == 0 || nphys + src_total_new(opts) > cap);
     if (opts.rlx) throw lcx_error("libcloudph++: aerosol relaxation was switched off in opts_init");
     adjust_timesteps(opts.dt);
     rng_recs.clear();
     last_async_coal = opts.coal != 0;
-    coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && sstp_coal == 1;   // (= the fused move below; with coalescence
+    coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
                                                        // substeps a used-up SD still takes part in the later ones and keeps its cell)
     hskpng_Tpr(opts.sedi || opts.coal || opts.cond);
     if (opts.sedi || opts.coal || opts.cond) hskpng_vterm(false);
@@ -2040,9 +2189,24 @@ struct Particles : IParticles {
     turb_adve_now = opts.turb_adve;
     // > 0 dimensions: advection + sedimentation + boundary + re-indexing in ONE pass over the positions; with a decomposed
     // domain the histogram is completed by the immigrants in migrate_finish
-    const bool fused = n_dims > 0 && nphys > 0 && !opts.rcyc;
+    const bool fused = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain;
+    hold_big_list = fused && src_now;
     move(opts.adve, opts.sedi, opts.subs, true, fused);
+    hold_big_list = false;
     adve_scheme = o.adve_scheme;
+    // The reference appends the source's super-droplets before the boundary conditions (particles_step.ipp:448-479); here those are
+    // inside the move, so the append comes after them.  That cannot be observed: a new super-droplet is drawn strictly inside its cell
+    // and inside [x0, x1) x [y0, y1) x [z0, z1), so no boundary rule applies to it.
+    if (src_now) {
+      const size_t n_old = nphys;
+      src(opts);                                     // (fused: there is room, see src_plain -- nothing is compacted under the move's histogram)
+      if (fused) {                                   // (not distmem) the newcomers' cells, histogram, ranks; those with n == 0 counted dead
+        if (nphys > n_old)
+          hipLaunchKernelGGL(k_ijk_hist<T>, dim3(nblk(nphys - n_old)), dim3(BS), 0, st, n_old, nphys, g, A.n.p, A.x.p, A.y.p, A.z.p, ijk.p, cell_cnt.p, rnk(), 1, d_dead_p());
+        list_big_from_hist();
+      }
+    }
+    if (opts.src) ++src_stp_ctr; else src_stp_ctr = 0;                                   // particles_step.ipp:476-479
     fused_pending = fused && distmem();
     n_before_unpack = nphys;
     if (fused && !distmem()) post_copy_after_fused_move(opts);
@@ -2284,6 +2448,7 @@ struct Particles : IParticles {
     hskpng_ijk();
     for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0 && n) HIPCHK(hipMemsetAsync(A.ext[ix].p, 0, n * sizeof(T), st));
     if (ix_tag >= 0 && n) hipLaunchKernelGGL(k_fill_index<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_tag].p, n);
+    tag_next = n;
     if (use_rc2 && n) { hipLaunchKernelGGL(k_fill<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_rc2].p, n, T(-1)); hskpng_approximate_rc2_invalid(); }
     sstp_save();
     hskpng_count();

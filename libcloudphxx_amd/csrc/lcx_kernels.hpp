@@ -316,7 +316,8 @@ __device__ __forceinline__ uint32_t wave_hist_rank(uint32_t *cnt, uint32_t c, bo
 // and take no part in the histogram, so they never enter the sorted order.
 template <class T>
 __global__ void __launch_bounds__(BS)
-k_ijk_hist(size_t first, size_t n, grid_t g, const n_t *mult, const T *x, const T *y, const T *z, uint32_t *ijk, uint32_t *cnt, uint32_t *rank, int do_ijk)
+k_ijk_hist(size_t first, size_t n, grid_t g, const n_t *mult, const T *x, const T *y, const T *z, uint32_t *ijk, uint32_t *cnt, uint32_t *rank, int do_ijk,
+           unsigned int *dead_count = nullptr /* do_ijk == 1: counts the SDs found with n == 0 (the aerosol source's newcomers behind a fused move) */)
 {
   const size_t i = first + gid();                    // [first, n): the whole storage, or only the immigrants appended by unpack
   bool active = i < n;
@@ -325,7 +326,7 @@ k_ijk_hist(size_t first, size_t n, grid_t g, const n_t *mult, const T *x, const 
     // do_ijk: 0 keep ijk; 1 removal point (post_copy): n == 0 leaves the order; 2 plain hskpng_ijk: an SD with n == 0 stays in
     // the order until the next removal point, exactly as in the reference (e.g. zero-multiplicity SDs right after init)
     if (do_ijk) {
-      if (do_ijk == 1 ? mult[i] == 0 : ijk[i] == DEAD_CELL) c = DEAD_CELL;
+      if (do_ijk == 1 ? mult[i] == 0 : ijk[i] == DEAD_CELL) { c = DEAD_CELL; if (dead_count) atomicAdd(dead_count, 1u); }
       else c = cell_of(g, g.nx ? x[i] : T(0), g.ny ? y[i] : T(0), g.nz ? z[i] : T(0));
       ijk[i] = c;
     } else c = ijk[i];
@@ -2936,14 +2937,15 @@ __global__ void k_cell_max(size_t n_cell, const uint32_t *cell_start, const uint
 // ============================================================================================
 template <class T>
 __global__ void k_init_dry(size_t n_new, size_t n_old, n_t per_cell, T log_rd_min, T log_rd_max, u01_src<T> rs,
-                           uint32_t *ijk, T *rd3, T *kpa, T kappa, T *vt, T *lnrd_out = nullptr /* the drawn ln(rd) itself, for the host (see init_SD_with_distros) */)
+                           uint32_t *ijk, T *rd3, T *kpa, T kappa, T *vt, T *lnrd_out = nullptr /* the drawn ln(rd) itself, for the host (see init_SD_with_distros) */,
+                           const uint32_t *cells = nullptr /* aerosol source: the c-th group of per_cell goes to cell cells[c] (init_count_num_src) */)
 {
   const size_t gI = gid(); if (gI >= n_new) return;
   const size_t c = gI / per_cell;                                            // init_ijk.ipp:36-52 (cell-major)
   const size_t ptr = size_t(per_cell) * c;
   const T u = rs.arr ? rs.arr[gI] : philox::u01<T>(gI, rs.call, rs.seed);
   const T lnrd = log_rd_min + T(T(gI - ptr) + u) * (log_rd_max - log_rd_min) / T(per_cell);   // init_dry_sd_conc.ipp:26-34
-  ijk[n_old + gI] = uint32_t(c);
+  ijk[n_old + gI] = cells ? cells[c] : uint32_t(c);
   rd3[n_old + gI] = exp(3 * lnrd);
   if (lnrd_out) lnrd_out[gI] = lnrd;
   kpa[n_old + gI] = kappa;
@@ -2970,10 +2972,11 @@ __global__ void k_init_const_multi(size_t n_new, size_t n_old, const uint32_t *c
 // concentration (conc_to_number, init_count_num.ipp:41-70, and init_n.ipp:130-143)
 template <class T>
 __global__ void k_init_sizes(size_t n_new, size_t n_old, n_t per_cell, T rad3, T kappa, T conc0, const T *dv, const T *rhod,
-                             const T *conc_factor, int nz, int indep_rhod, uint32_t *ijk, T *rd3, T *kpa, T *vt, n_t *n)
+                             const T *conc_factor, int nz, int indep_rhod, uint32_t *ijk, T *rd3, T *kpa, T *vt, n_t *n,
+                             const uint32_t *cells = nullptr /* aerosol source: as in k_init_dry */)
 {
   const size_t gI = gid(); if (gI >= n_new) return;
-  const size_t c = gI / per_cell, p = n_old + gI;
+  const size_t c = cells ? size_t(cells[gI / per_cell]) : gI / per_cell, p = n_old + gI;
   ijk[p] = uint32_t(c); rd3[p] = rad3; kpa[p] = kappa; vt[p] = T(-1);
   T conc = conc0;
   conc = conc * dv[c];
@@ -3033,6 +3036,51 @@ __global__ void k_init_pos(size_t n_new, size_t n_old, int dim, grid_t g, const 
   const T u = rs.arr ? rs.arr[gI] : philox::u01<T>(gI, rs.call, rs.seed);
   pos[p] = u * mn(p1, T((ii + 1) * dp)) + (1. - u) * mx(p0, T(ii * dp));
 }
+
+// ============================================================================================
+// aerosol source, src_type = matching (src_dry_distros_matching.ipp:50-417)
+// ============================================================================================
+// The source's candidates -- sd_conc per cell of the source box, the j-th of a cell drawn inside the j-th of the cell's sd_conc bins of
+// ln rd -- already lie behind the old super-droplets, initialised as for src_type = simple (multiplicity included).  One workgroup
+// per source cell: every old super-droplet of the cell (the cell-sorted order) is binned by ln rd; a bin that holds old super-droplets
+// hands its candidate's multiplicity to ONE of them and the candidate is left with n = 0, which the step's post_copy removes like any
+// used-up super-droplet; a candidate whose bin is empty stays.
+// Which old super-droplet of a bin: the reference sorts by (cell, rd3) and takes number u01 * count of the bin.  Any uniform pick
+// inside the bin is the same distribution, so nothing is sorted by rd3 here: every old super-droplet draws a 32-bit Philox key at its
+// position in the sorted order and the smallest (key, position) of the bin wins -- an LDS atomic minimum on 64 bits, whose result
+// does not depend on the order in which the lanes arrive, so a run is reproducible.
+// LDS: 8 B per bin (n_bins <= SRC_MATCH_MAX_BINS); grid = source cells.
+constexpr int SRC_MATCH_MAX_BINS = 4096;
+template <class T>
+__global__ void __launch_bounds__(BS) k_src_match(const uint32_t *cells, uint32_t n_bins, T log_rd_min, T log_rd_max, const uint32_t *cell_start,
+                                                  const uint32_t *sorted_id, const T *rd3, n_t *n, size_t n_old, uint64_t call, uint64_t seed)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned long long src_win[];      // (no static LDS in this kernel: the base is aligned)
+  constexpr unsigned long long NONE = ~0ull;
+  for (uint32_t b = threadIdx.x; b < n_bins; b += BS) src_win[b] = NONE;
+  __syncthreads();
+  const uint32_t c = cells[blockIdx.x], s = cell_start[c], e = cell_start[c + 1];
+  for (uint32_t q = s + threadIdx.x; q < e; q += BS) {
+    const uint32_t id = sorted_id[q];
+    if (size_t(id) >= n_old) continue;                                       // (candidates are not in the sorted order; belt and braces)
+    const T lnrd = log(rd3[id]) / T(3);
+    if (lnrd < log_rd_min || !(lnrd < log_rd_max)) continue;                 // get_bin_no: out of bins
+    const uint32_t b = uint32_t((lnrd - log_rd_min) / (log_rd_max - log_rd_min) * T(n_bins));
+    if (b >= n_bins) continue;
+    const unsigned long long key = (static_cast<unsigned long long>(philox::un(q, call, seed)) << 32) | (q - s);
+    atomicMin(&src_win[b], key);
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < n_bins; b += BS) {
+    const unsigned long long w = src_win[b];
+    if (w == NONE) continue;
+    const size_t cand = n_old + size_t(blockIdx.x) * n_bins + b;             // bins of different lanes hold different super-droplets: no race
+    const uint32_t id = sorted_id[s + uint32_t(w)];
+    n[id] += n[cand];
+    n[cand] = 0;
+  }
+}
+template <class T> __global__ void k_fill_index_from(T *a, size_t n, T first) { size_t i = gid(); if (i < n) a[i] = first + T(i); }
 
 // ============================================================================================
 // 1-D domain decomposition: migrant lists, pack, unpack (bcnd.ipp:160-205, pack.ipp:14-133, unpack.ipp:14-143)

@@ -117,6 +117,11 @@ struct MultiParticles : IParticles {
         if (i != 0) o.x0 = 0.;
         if (i != D - 1) o.x1 = o.nx * o.dx; else o.x1 = oi.x1 - bfr * oi.dx;
         o.n_sd_max = oi.n_sd_max / D + 1;
+        // the aerosol source's box in the slab's frame, clipped to the slab; a slab that the box does not touch gets
+        // src_x0 = src_x1 = 0, which is how step_async knows to skip it (distmem_opts.hpp:31-45)
+        o.src_x0 = oi.src_x0 - bfr * oi.dx; o.src_x1 = oi.src_x1 - bfr * oi.dx;
+        if (o.src_x1 <= o.x0 || o.src_x0 >= o.x1) o.src_x0 = o.src_x1 = 0;
+        else { if (o.src_x0 < o.x0) o.src_x0 = o.x0; if (o.src_x1 > o.x1) o.src_x1 = o.x1; }
         const bool first = i == 0, last = i == D - 1;
         o.bcond_lft = first && !periodic ? 3 : 1;                                  // particles_multi_gpu_impl.ipp:158-179
         o.bcond_rgt = last && !periodic ? 3 : 1;

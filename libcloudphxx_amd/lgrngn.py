@@ -194,13 +194,26 @@ class _opts_init_c(C.Structure):
         ("n_x_tot", C.c_int), ("n_x_bfr", C.c_int), ("bcond_lft", C.c_int), ("bcond_rgt", C.c_int),
         ("strict_fp", C.c_int), ("cond_solver", C.c_int), ("reorder_every", C.c_int), ("stream_ordered", C.c_int),
         ("dbg_flags", C.c_uint), ("dbg_cond_budget", C.c_int), ("dbg_pack_delay_us", C.c_int),
+        ("src_x0", C.c_double), ("src_y0", C.c_double), ("src_z0", C.c_double),
+        ("src_x1", C.c_double), ("src_y1", C.c_double), ("src_z1", C.c_double),
     ]
+
+
+class _src_distro_c(C.Structure):
+    _fields_ = [("distro", _distro_c), ("sd_conc", C.c_ulonglong), ("supstp", C.c_int)]
+
+
+class _src_size_c(C.Structure):
+    _fields_ = [("kappa", C.c_double), ("rd_insol", C.c_double), ("radius", C.c_double), ("conc_per_s", C.c_double),
+                ("sd_count", C.c_int), ("supstp", C.c_int)]
 
 
 class _opts_c(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("adve", "sedi", "subs", "cond", "coal", "src", "rlx", "rcyc", "turb_adve",
                                         "turb_cond", "turb_coal", "ice_nucl", "chem_dsl", "chem_dsc", "chem_rct")] + \
-               [("RH_max", C.c_double), ("dt", C.c_double)]
+               [("RH_max", C.c_double), ("dt", C.c_double),
+                ("src_dry_distros", C.POINTER(_src_distro_c)), ("n_src_dry_distros", C.c_int),
+                ("src_dry_sizes", C.POINTER(_src_size_c)), ("n_src_dry_sizes", C.c_int)]
 
 
 class _arrinfo_c(C.Structure):
@@ -233,6 +246,22 @@ class expvolume:
     def __call__(self, lnrd):
         q = np.exp(lnrd) ** 3 / self.r_zero ** 3
         return float(self.n_zero * 3. * q * np.exp(-q))
+
+
+def _fill_distro(d, key, fun, keep):
+    """one lcx_distro_t from a (kappa, rd_insol) key and a spectrum: built-in forms natively, anything else as a host callback"""
+    d.kappa, d.rd_insol = float(key[0]), float(key[1])
+    if isinstance(fun, lognormal):
+        d.n_modes = len(fun.mean_rd)
+        for m in range(len(fun.mean_rd)):
+            d.mean_rd[m], d.sdev[m], d.n_stp[m] = fun.mean_rd[m], fun.sdev[m], fun.n_stp[m]
+    elif isinstance(fun, expvolume):
+        d.n_modes = -1
+        d.mean_rd[0], d.n_stp[0] = fun.r_zero, fun.n_zero
+    else:
+        cb = DISTRO_FN(lambda lnrd, user, _f=fun: float(_f(lnrd)))
+        keep.append(cb)
+        d.fn = cb
 
 
 class opts_init_t:
@@ -287,10 +316,11 @@ class opts_init_t:
         self.th_dry = True
         self.const_p = False
         self.diag_incloud_time = False
-        # fields of the parts that are outside this library (chemistry, aerosol sources / relaxation): kept so that scripts written
+        # box of the aerosol source (src_type simple / matching; the spectra are in opts_t)
+        self.src_x0 = self.src_y0 = self.src_z0 = self.src_x1 = self.src_y1 = self.src_z1 = 0.
+        # fields of the parts that are outside this library (chemistry, relaxation): kept so that scripts written
         # for the reference can set and print them; the matching switches make the constructor throw
         self.chem_rho = 0.
-        self.src_x0 = self.src_y0 = self.src_z0 = self.src_x1 = self.src_y1 = self.src_z1 = 0.
         self.rlx_dry_distros = {}
         self.rlx_bins, self.rlx_timescale, self.rlx_sd_per_bin, self.supstp_rlx = 0, 1., 0., 1
         # extensions (include/lcx.h)
@@ -326,19 +356,7 @@ class opts_init_t:
         keys = sorted(self.dry_distros.keys())
         darr = (_distro_c * max(1, len(keys)))()
         for i, k in enumerate(keys):
-            fun = self.dry_distros[k]
-            darr[i].kappa, darr[i].rd_insol = float(k[0]), float(k[1])
-            if isinstance(fun, lognormal):
-                darr[i].n_modes = len(fun.mean_rd)
-                for m in range(len(fun.mean_rd)):
-                    darr[i].mean_rd[m], darr[i].sdev[m], darr[i].n_stp[m] = fun.mean_rd[m], fun.sdev[m], fun.n_stp[m]
-            elif isinstance(fun, expvolume):
-                darr[i].n_modes = -1
-                darr[i].mean_rd[0], darr[i].n_stp[0] = fun.r_zero, fun.n_zero
-            else:
-                cb = DISTRO_FN(lambda lnrd, user, _f=fun: float(_f(lnrd)))
-                keep.append(cb)
-                darr[i].fn = cb
+            _fill_distro(darr[i], k, self.dry_distros[k], keep)
         keep.append(darr)
         c.dry_distros = C.cast(darr, C.POINTER(_distro_c))
         c.n_dry_distros = len(keys)
@@ -368,15 +386,45 @@ class opts_t:
         self.RH_max = 44.
         self.dt = -1.
         self.chem = False    # accepted for source compatibility with the reference's tests (no-op)
-        self.chem_gas = {}   # ambient trace gases, aerosol sources: holders only (chemistry / sources are outside this library)
+        self.chem_gas = {}   # ambient trace gases: a holder only (chemistry is outside this library)
+        # aerosol source (opts_init.src_type): {(kappa, rd_insol): (spectrum per second, sd_conc, supstp)} and
+        # {(kappa, rd_insol): {radius: [concentration per second, sd_count, supstp]}}
         self.src_dry_distros = {}
         self.src_dry_sizes = {}
 
     def _to_c(self):
         c = _opts_c()
         for name, ctype in _opts_c._fields_:
+            if ctype is not C.c_double and ctype is not C.c_int or name.startswith("n_src_"):
+                continue
             v = getattr(self, name)
             setattr(c, name, float(v) if ctype is C.c_double else int(bool(v)))
+        if not self.src_dry_distros and not self.src_dry_sizes:
+            return c                                   # (null pointers, zero counts)
+        keep = []                                      # callbacks and arrays live as long as the struct the caller holds
+        keys = sorted(self.src_dry_distros.keys())     # std::map order
+        if keys:
+            darr = (_src_distro_c * len(keys))()
+            for i, k in enumerate(keys):
+                fun, sd_conc, supstp = self.src_dry_distros[k]
+                _fill_distro(darr[i].distro, k, fun, keep)
+                darr[i].sd_conc, darr[i].supstp = int(sd_conc), int(supstp)
+            keep.append(darr)
+            c.src_dry_distros = C.cast(darr, C.POINTER(_src_distro_c))
+            c.n_src_dry_distros = len(keys)
+        flat = []
+        for k in sorted(self.src_dry_sizes.keys()):
+            for r in sorted(self.src_dry_sizes[k].keys()):
+                conc, cnt, supstp = self.src_dry_sizes[k][r]
+                flat.append((float(k[0]), float(k[1]), float(r), float(conc), int(cnt), int(supstp)))
+        if flat:
+            sarr = (_src_size_c * len(flat))()
+            for i, t in enumerate(flat):
+                sarr[i].kappa, sarr[i].rd_insol, sarr[i].radius, sarr[i].conc_per_s, sarr[i].sd_count, sarr[i].supstp = t
+            keep.append(sarr)
+            c.src_dry_sizes = C.cast(sarr, C.POINTER(_src_size_c))
+            c.n_src_dry_sizes = len(flat)
+        c._keep = keep
         return c
 
 

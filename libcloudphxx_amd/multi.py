@@ -47,6 +47,9 @@ def get_dev_nx(nx, rank, size):
 def distmem_opts(opts_init, rank, size, self_ring=False):
     """Per-rank copy of opts_init for the slab owned by `rank` (distmem_opts.hpp:20-52).
     Returns (local opts_init, n_x_bfr)."""
+    if int(opts_init.src_type) != 0:
+        raise RuntimeError("libcloudph++: aerosol sources: use the multi-device object (factory(backend_t.multi_HIP, ...)); "
+                           "the one-process-per-GPU path does not carry them")
     oi = copy.copy(opts_init)
     oi.dry_distros = dict(opts_init.dry_distros)
     n_x_bfr = rank * get_dev_nx(opts_init.nx, 0, size)
