@@ -70,11 +70,17 @@ typedef struct {
 /* one (kappa, radius) -> (STP concentration, SD count) entry of dry_sizes_t (distro_t.hpp:39-46) */
 typedef struct { double kappa, rd_insol, radius, conc; int sd_count; } lcx_dry_size_t;
 
+/* one entry of rlx_dry_distros_t (opts_init.hpp): the spectrum n(ln rd) at STP that aerosol relaxation restores (distro.kappa: the
+ * map's key = the hygroscopicity given to what it creates; distro.rd_insol unused), among the super-droplets with
+ * kappa_min <= kappa < kappa_max, in the levels int(z_min / dz) <= k < int(z_max / dz) */
+typedef struct { lcx_distro_t distro; double kappa_min, kappa_max, z_min, z_max; } lcx_rlx_distro_t;
+
 /* POD mirror of opts_init_t<real_t> (opts_init.hpp:29-253); same field names and defaults.
- * Fields of sub-systems that are out of scope (chemistry, ice, relaxation) are kept so that a
+ * Fields of sub-systems that are out of scope (chemistry, ice) are kept so that a
  * caller's settings are checked, not silently dropped: lcx_create() fails if one of them is
  * switched on.  The aerosol source (src_type simple / matching, the box src_x0 .. src_z1 here,
- * the spectra in lcx_opts_t) is built. */
+ * the spectra in lcx_opts_t) and aerosol relaxation (rlx_switch, the rlx_* fields at the end) are built;
+ * the two together in one object are refused. */
 typedef struct {
   int nx, ny, nz;
   double dx, dy, dz, dt;
@@ -154,7 +160,17 @@ typedef struct {
   /* box in which the aerosol source creates super-droplets (opts_init.hpp: src_x0 .. src_z1, default 0; src_type above:
    * 0 off, 1 simple, 2 matching, ccn_source.hpp).  src_x0 == src_x1 == 0 switches the source of this domain off. */
   double src_x0, src_y0, src_z0, src_x1, src_y1, src_z1;
+  /* aerosol relaxation (rlx_switch; opts_init.hpp: rlx_bins 0, rlx_sd_per_bin 0, rlx_timescale 1, supstp_rlx 1, no spectra): every
+   * supstp_rlx steps with opts.rlx, per spectrum, size bin and level, the super-droplets that the horizontal sum of the multiplicities
+   * misses against the spectrum are created (rlx_dry_distros.ipp).  rlx_bins: size bins shared by the spectra in proportion to their
+   * ranges of ln rd, at most LCX_RLX_MAX_BINS (the census keeps a level's bins in one workgroup's LDS; up to this many its time hardly depends on
+   * the number of bins -- 0-3 % -- above it it begins to: EXPERIMENTS.md 7.2). */
+  int rlx_bins, supstp_rlx;
+  double rlx_sd_per_bin, rlx_timescale;
+  const lcx_rlx_distro_t *rlx_dry_distros;                  /* sorted by kappa like std::map */
+  int n_rlx_dry_distros;
 } lcx_opts_init_t;
+#define LCX_RLX_MAX_BINS 1024
 
 enum lcx_dbg {
   LCX_DBG_NO_COND_PRE = 1 << 0,        /* fast arithmetic: evaluate the per-cell set-up of the growth rate per droplet (k_cond<T, true>) */
@@ -199,6 +215,8 @@ enum lcx_dbg {
                                         * every substep of the step in one launch (k_cond_substeps: the same bits) */
   LCX_DBG_VTERM_INVALID_OWN_PASS = 1 << 28, /* sstp_coal > 1: hskpng_vterm_invalid as a launch of its own between the substeps (rounds 1-5) instead of on the
                                         * next substep's in-cell ranking (the same bits) */
+  LCX_DBG_RLX_GLOBAL_ATOMICS = 1 << 29, /* aerosol relaxation, measured and not adopted (5 x slower; the tests' cross-check of the census table): the census as one pass in storage order with a global 64-bit atomic
+                                        * per counted droplet (k_rlx_census_global) instead of the per-level table in LDS (the same counts) */
   LCX_DBG_COND_TOMS_TWO_PASS = 1 << 15 /* cond_solver = 1 through round 2's kernels (k_cond_fast_fold + k_cond_fast over the sorted order, iteration budget and
                                         * straggler launch) instead of the storage-order kernel with TOMS748 in it */
 };
@@ -256,6 +274,7 @@ const char *lcx_version(void);
 
 /* factory<real_t>(backend, opts_init)  (factory.hpp:12-15, src/lib.cpp:13-40) + ctor (particles_ctor.ipp:22-75) */
 int lcx_create(const lcx_opts_init_t *, int real_kind, lcx_particles **out);
+/* (aerosol relaxation's size bins without a device: lcx_rlx_layout, include/lcx_rlx.h) */
 void lcx_destroy(lcx_particles *);
 /* factory<real_t>(multi_CUDA | multi_HIP, opts_init): ONE object that drives opts_init.dev_count devices of this process (0: all
  * visible ones) -- replaces particles_t<real_t, multi_CUDA> (particles.hpp:246-340, src/particles_multi_gpu_*.ipp,

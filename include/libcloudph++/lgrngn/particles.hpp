@@ -7,6 +7,7 @@
 // -> step_async, diag_* in between), same ownership (caller owns every array; th / rv are written back at
 // the end of step_cond; outbuf() points into library memory valid until the next outbuf()).
 #pragma once
+#include <algorithm>
 #include "extincl.hpp"
 #include "opts.hpp"
 #include "opts_init.hpp"
@@ -113,7 +114,6 @@ namespace libcloudphxx { namespace lgrngn {
     // multi: the object spans opts_init.dev_count devices (lcx_create_multi) -- used by the multi_HIP specialisation below
     explicit particles_t(opts_init_t<real_t> oi, int n_x_tot = 0, bool multi = false) : pimpl(new impl)
     {
-      if (!oi.rlx_dry_distros.empty()) throw std::runtime_error("libcloudph++: option outside the accelerated hot path (rlx)");
       pimpl->opts_init = oi;
       this->opts_init = &pimpl->opts_init;
       lcx_opts_init_t c;
@@ -157,6 +157,19 @@ namespace libcloudphxx { namespace lgrngn {
       for (const auto &kv : o.dry_sizes) for (const auto &rc : kv.second)
         ds.push_back(lcx_dry_size_t{double(kv.first.kappa), double(kv.first.rd_insol), double(rc.first), double(rc.second.first), rc.second.second});
       c.dry_sizes = ds.data(); c.n_dry_sizes = int(ds.size());
+      // aerosol relaxation: an unordered_map in the reference, sorted by kappa here (the order the library expects)
+      c.rlx_bins = int(o.rlx_bins); c.rlx_sd_per_bin = o.rlx_sd_per_bin; c.rlx_timescale = o.rlx_timescale; c.supstp_rlx = o.supstp_rlx;
+      std::vector<lcx_rlx_distro_t> rd;
+      for (const auto &kv : pimpl->opts_init.rlx_dry_distros) {
+        lcx_rlx_distro_t e{};
+        e.distro.kappa = kv.first;
+        e.distro.fn = &detail::distro_trampoline<real_t>; e.distro.user = std::get<0>(kv.second).get();   // shared_ptr kept alive by pimpl->opts_init
+        e.kappa_min = std::get<1>(kv.second).first; e.kappa_max = std::get<1>(kv.second).second;
+        e.z_min = std::get<2>(kv.second).first; e.z_max = std::get<2>(kv.second).second;
+        rd.push_back(e);
+      }
+      std::sort(rd.begin(), rd.end(), [](const lcx_rlx_distro_t &a, const lcx_rlx_distro_t &b) { return a.distro.kappa < b.distro.kappa; });
+      c.rlx_dry_distros = rd.empty() ? nullptr : rd.data(); c.n_rlx_dry_distros = int(rd.size());
       detail::lcx_check(multi ? lcx_create_multi(&c, int(sizeof(real_t)), &pimpl->h) : lcx_create(&c, int(sizeof(real_t)), &pimpl->h));
     }
     ~particles_t() override {}

@@ -22,6 +22,7 @@
 
 #include <atomic>
 #include "../../include/lcx.h"
+#include "../../include/lcx_rlx.h"
 #include "lcx_kernels.hpp"
 #include "lcx_pool.hpp"
 
@@ -151,6 +152,99 @@ struct IParticles {
   virtual void *stream() { return nullptr; }
 };
 
+// ---- host-side spectrum analysis shared by the object and by the entries that need no device (lcx_rlx_layout) ----
+static double eval_distro_host(const lcx_distro_t &d, double lnrd)
+{
+  if (d.fn) return d.fn(lnrd, d.user);
+  double res = 0;
+  if (d.n_modes < 0) { const double q = std::pow(std::exp(lnrd), 3) / std::pow(d.mean_rd[0], 3); return d.n_stp[0] * 3. * q * std::exp(-q); }
+  for (int m = 0; m < d.n_modes; ++m)
+    res += d.n_stp[m] / std::sqrt(2 * M_PI) / std::log(d.sdev[m]) * std::exp(-std::pow((lnrd - std::log(d.mean_rd[m])), 2) / 2. / std::pow(std::log(d.sdev[m]), 2));
+  return res;
+}
+// init_dist_analysis.ipp:17-77 in real_t = T.  dt_: 1 at initialisation; the aerosol source's spectrum is per second and the entry
+// stands for supstp * dt seconds of it
+template <class T>
+static void dist_analysis_sd_conc(const lcx_opts_init_t &o, int n_dims, const lcx_distro_t &d, n_t sd_conc, T dv0, T dt_, double &multiplier, double &log_rd_min, double &log_rd_max)
+{
+  const T vol = n_dims == 0 ? dv0 : T(T(o.dx) * T(o.dy) * T(o.dz));
+  if (o.rd_min >= 0 && o.rd_max >= 0) {
+    const T rd_min = T(o.rd_min), rd_max = T(o.rd_max);
+    multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
+    log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
+  } else if (o.rd_min < 0 && o.rd_max < 0) {
+    T rd_min = T(1e-14), rd_max = T(1e-3);                                             // config.hpp:23-24
+    bool found = false;
+    while (!found) {
+      multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
+      log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
+      const n_t n_min = n_t(T(eval_distro_host(d, log_rd_min)) * T(multiplier)), n_max = n_t(T(eval_distro_host(d, log_rd_max)) * T(multiplier));
+      if (rd_min == T(1e-14) && n_min != 0) throw lcx_error("Initial dry radii distribution is non-zero (" + std::to_string(n_min) + ") for rd_min_init (1e-14)");
+      if (rd_max == T(1e-3) && n_max != 0) throw lcx_error("Initial dry radii distribution is non-zero (" + std::to_string(n_max) + ") for rd_max_init (0.001)");
+      if (n_min == 0) rd_min *= T(1.01); else if (n_max == 0) rd_max /= T(1.01); else found = true;
+    }
+  } else throw lcx_error("opts_init.rd_min * opts_init.rd_max < 0");
+}
+static int n_dims_of(const lcx_opts_init_t &o) { auto m = [](int n) { return n == 0 ? 1 : n; }; return o.nx / m(o.nx) + o.ny / m(o.ny) + o.nz / m(o.nz); }
+
+// ---- aerosol relaxation: what does not depend on the step (rlx_dry_distros.ipp:100-147,186-187), in real_t = T ----
+template <class T> struct RlxTables {
+  std::vector<rlx_spec<T>> specs;       // one per entry of rlx_dry_distros
+  std::vector<T> edges, conc;           // bin edges in rd3 (n_bins + 1 per spectrum), expected STP concentration per bin
+  std::vector<int> bin_spec;            // bin -> spectrum
+  int tot_bins = 0;
+};
+// the constructor's checks of the relaxation options (init_sanity_check.ipp:134-141 and what the reference only asserts)
+static void rlx_check_opts(const lcx_opts_init_t &o)
+{
+  if (n_dims_of(o) < 2) throw lcx_error("libcloudph++: CCN relaxation works only in 2D and 3D, set rlx_switch to false");
+  if (o.rlx_bins <= 0) throw lcx_error("libcloudph++: rlx_bins <= 0");
+  if (!(o.rlx_sd_per_bin > 0)) throw lcx_error("libcloudph++: rlx_sd_per_bin <= 0");
+  if (!(o.rlx_timescale > 0)) throw lcx_error("libcloudph++: rlx_timescale <= 0");
+  if (o.supstp_rlx <= 0) throw lcx_error("libcloudph++ (HIP): supstp_rlx must be greater than 0");
+  if (o.rlx_bins > LCX_RLX_MAX_BINS)
+    throw lcx_error("libcloudph++ (HIP): rlx_bins above " + std::to_string(LCX_RLX_MAX_BINS) + " (the census keeps the bins of a level in one workgroup's LDS)");
+  if (o.n_rlx_dry_distros < 0 || (o.n_rlx_dry_distros > 0 && !o.rlx_dry_distros)) throw lcx_error("libcloudph++ (HIP): rlx_dry_distros is not set");
+  for (int i = 0; i < o.n_rlx_dry_distros; ++i) {
+    const lcx_rlx_distro_t &e = o.rlx_dry_distros[i];
+    if (!(e.z_min >= 0) || e.z_min > e.z_max) throw lcx_error("libcloudph++ (HIP): rlx_dry_distros: altitude range with z_min < 0 or z_min > z_max");
+    if (!(e.kappa_min < e.kappa_max)) throw lcx_error("libcloudph++ (HIP): rlx_dry_distros: empty kappa range (kappa_min >= kappa_max)");
+    if (!(e.distro.kappa >= 0)) throw lcx_error("libcloudph++ (HIP): rlx_dry_distros: kappa < 0");
+  }
+}
+template <class T> static RlxTables<T> rlx_make_tables(const lcx_opts_init_t &o)
+{
+  RlxTables<T> t;
+  const int nd = n_dims_of(o), ns = o.n_rlx_dry_distros;
+  std::vector<T> lo(ns), rng(ns);
+  T tot_lnrd_rng = 0;
+  for (int i = 0; i < ns; ++i) {
+    double mult, a, b;
+    dist_analysis_sd_conc<T>(o, nd, o.rlx_dry_distros[i].distro, n_t(o.rlx_bins), T(0), T(1), mult, a, b);
+    lo[i] = T(a); rng[i] = T(T(b) - T(a));
+    tot_lnrd_rng += rng[i];
+  }
+  for (int i = 0; i < ns; ++i) {
+    const lcx_rlx_distro_t &e = o.rlx_dry_distros[i];
+    const int n_bins = int(o.rlx_bins * rng[i] / tot_lnrd_rng);
+    if (!(rng[i] > 0) || n_bins <= 0) throw lcx_error("libcloudph++ (HIP): rlx_dry_distros: a spectrum is left without size bins (rlx_bins too small for its share of ln rd)");
+    const T bin = rng[i] / n_bins;
+    rlx_spec<T> s;
+    s.kpa_min = T(e.kappa_min); s.kpa_max = T(e.kappa_max); s.log_rd_min = lo[i]; s.bin_size = bin; s.inv_bin_size = T(1) / bin; s.kappa = T(e.distro.kappa);
+    s.bin0 = t.tot_bins; s.n_bins = n_bins; s.edge0 = t.tot_bins + i;
+    s.k_lo = int(T(e.z_min) / T(o.dz)); s.k_hi = std::min(int(T(e.z_max) / T(o.dz)), o.nz);      // (the reference asserts z_max_index < nz)
+    for (int b = 0; b <= n_bins; ++b) t.edges.push_back(T(std::exp(T(3) * (lo[i] + T(b) * bin))));
+    for (int b = 0; b < n_bins; ++b) {
+      const T centre = T(lo[i] + (b + 0.5) * bin);
+      t.conc.push_back(T(T(eval_distro_host(e.distro, centre)) * bin));
+      t.bin_spec.push_back(i);
+    }
+    t.specs.push_back(s);
+    t.tot_bins += n_bins;
+  }
+  return t;
+}
+
 template <class real_t>
 struct Particles : IParticles {
   using T = real_t;
@@ -254,8 +348,15 @@ struct Particles : IParticles {
   // ------------------------------------------------------------------------------------------
   explicit Particles(const lcx_opts_init_t &oi) : o(oi)
   {
-    if (oi.chem_switch || oi.ice_switch || oi.rlx_switch)
+    // (relaxation is built, a source is built, the two in one object are not: DESIGN.md section 8)
+    if (oi.chem_switch || oi.ice_switch || (oi.rlx_switch && oi.src_type))
       throw lcx_error("libcloudph++: option outside the accelerated hot path (chem/ice/rlx)");
+    if (oi.rlx_switch) {
+      rlx_check_opts(oi);
+      rlx_distros.assign(oi.rlx_dry_distros, oi.rlx_dry_distros + oi.n_rlx_dry_distros);
+      o.rlx_dry_distros = rlx_distros.data();
+      rlx_tab = rlx_make_tables<T>(o);
+    }
     if (oi.src_type < 0 || oi.src_type > 2) throw lcx_error("libcloudph++: unknown opts_init.src_type");
     if (oi.n_sd_max >= (1ull << 32)) throw lcx_error("libcloudph++: n_sd_max must be < 2^32 per device (32-bit super-droplet ids)");
     distros.assign(oi.dry_distros, oi.dry_distros + oi.n_dry_distros);
@@ -322,6 +423,7 @@ struct Particles : IParticles {
     outbuf_h.assign(ncell, T(0));
     if (distmem()) alloc_mig();
     if (o.src_type && n_dims >= 2) list_src_cells();
+    if (o.rlx_switch) rlx_alloc();
   }
   ~Particles() override
   {
@@ -1590,36 +1692,10 @@ struct Particles : IParticles {
   // ------------------------------------------------------------------------------------------
   // initialisation (particles_init.ipp:16-131)
   // ------------------------------------------------------------------------------------------
-  double eval_distro(const lcx_distro_t &d, double lnrd) const
-  {
-    if (d.fn) return d.fn(lnrd, d.user);
-    double res = 0;
-    if (d.n_modes < 0) { const double q = std::pow(std::exp(lnrd), 3) / std::pow(d.mean_rd[0], 3); return d.n_stp[0] * 3. * q * std::exp(-q); }
-    for (int m = 0; m < d.n_modes; ++m)
-      res += d.n_stp[m] / std::sqrt(2 * M_PI) / std::log(d.sdev[m]) * std::exp(-std::pow((lnrd - std::log(d.mean_rd[m])), 2) / 2. / std::pow(std::log(d.sdev[m]), 2));
-    return res;
-  }
+  double eval_distro(const lcx_distro_t &d, double lnrd) const { return eval_distro_host(d, lnrd); }
   // dt_: 1 at initialisation; the aerosol source's spectrum is per second and the entry stands for supstp * dt seconds of it
   void init_dist_analysis_sd_conc(const lcx_distro_t &d, n_t sd_conc, T dv0, T dt_ = T(1))
-  {                                                                                      // init_dist_analysis.ipp:17-77
-    const T vol = n_dims == 0 ? dv0 : T(T(o.dx) * T(o.dy) * T(o.dz));
-    if (o.rd_min >= 0 && o.rd_max >= 0) {
-      const T rd_min = T(o.rd_min), rd_max = T(o.rd_max);
-      multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
-      log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
-    } else if (o.rd_min < 0 && o.rd_max < 0) {
-      T rd_min = T(1e-14), rd_max = T(1e-3);                                             // config.hpp:23-24
-      bool found = false;
-      while (!found) {
-        multiplier = T(std::log(rd_max / rd_min) / sd_conc * dt_ * vol);
-        log_rd_min = T(std::log(rd_min)); log_rd_max = T(std::log(rd_max));
-        const n_t n_min = n_t(T(eval_distro(d, log_rd_min)) * T(multiplier)), n_max = n_t(T(eval_distro(d, log_rd_max)) * T(multiplier));
-        if (rd_min == T(1e-14) && n_min != 0) throw lcx_error("Initial dry radii distribution is non-zero (" + std::to_string(n_min) + ") for rd_min_init (1e-14)");
-        if (rd_max == T(1e-3) && n_max != 0) throw lcx_error("Initial dry radii distribution is non-zero (" + std::to_string(n_max) + ") for rd_max_init (0.001)");
-        if (n_min == 0) rd_min *= T(1.01); else if (n_max == 0) rd_max /= T(1.01); else found = true;
-      }
-    } else throw lcx_error("opts_init.rd_min * opts_init.rd_max < 0");
-  }
+  { dist_analysis_sd_conc<T>(o, n_dims, d, sd_conc, dv0, dt_, multiplier, log_rd_min, log_rd_max); }   // init_dist_analysis.ipp:17-77
   // ---- constant-multiplicity and large-tail initialisation (host analysis as in the reference, sampling on the device) ----
   // Brent's minimiser: the reference calls boost::math::tools::brent_find_minima (init_dist_analysis.ipp:95); Boost is not
   // vendored by the reference and its version is not pinned, so this is the published algorithm (Brent 1973, ch. 5)
@@ -1953,6 +2029,105 @@ struct Particles : IParticles {
     for (int i = 0; i < opts.n_src_dry_sizes; ++i) if (src_fires(src_stp_ctr, opts.src_dry_sizes[i].supstp)) src_dry_size(opts.src_dry_sizes[i]);
     release_replay_keep();
   }
+  // ------------------------------------------------------------------------------------------
+  // aerosol relaxation (particles_step.ipp:461-479, rlx_dry_distros.ipp): opts_init.rlx_switch, opts.rlx.  Per firing: the census of
+  // the super-droplets that exist (k_rlx_census, queued BEFORE the move: the reference's relaxation sees the cells of the start of
+  // step_async, its ijk is not refreshed between adve and post_copy), the plan per (bin, level) and its scan, one read-back of the
+  // number to create, and behind the move the newcomers (k_rlx_create) with what every new super-droplet gets (src_finish_new).
+  // ------------------------------------------------------------------------------------------
+  std::vector<lcx_rlx_distro_t> rlx_distros; RlxTables<T> rlx_tab; std::vector<T> rlx_conc_h;
+  static_assert(RLX_MAX_BINS == LCX_RLX_MAX_BINS, "the kernels' cap is the header's");
+  DevBuf<rlx_spec<T>> rlx_specs; DevBuf<T> rlx_edges, rlx_conc, rlx_vol; DevBuf<int> rlx_bin_spec;
+  DevBuf<unsigned long long> rlx_count; DevBuf<uint32_t> rlx_create, rlx_off, rlx_tiles, rlx_total; DevBuf<n_t> rlx_mult;
+  size_t rlx_stp_ctr = 0, rlx_m = 0, rlx_max_new = 0, rlx_lds_bytes = 0; int rlx_k_first = 0, rlx_k_end = 0, rlx_n_per_bin = 1; bool rlx_any_fn = false;
+  void rlx_alloc()
+  {
+    const RlxTables<T> &t = rlx_tab;
+    if (t.specs.empty()) return;
+    rlx_m = size_t(t.tot_bins) * size_t(o.nz);
+    rlx_n_per_bin = std::max<int>(1, int(T(o.rlx_sd_per_bin) + 0.5));                    // calc_n_sd_to_create
+    rlx_k_first = o.nz; rlx_k_end = 0; rlx_max_new = 0;
+    for (const rlx_spec<T> &sp : t.specs) {
+      rlx_k_first = std::min(rlx_k_first, sp.k_lo); rlx_k_end = std::max(rlx_k_end, sp.k_hi);
+      if (sp.k_hi > sp.k_lo) rlx_max_new += size_t(sp.n_bins) * size_t(sp.k_hi - sp.k_lo) * size_t(rlx_n_per_bin);
+    }
+    for (const lcx_rlx_distro_t &e : rlx_distros) rlx_any_fn |= e.distro.fn != nullptr;
+    rlx_specs.alloc(t.specs.size()); rlx_edges.alloc(t.edges.size()); rlx_conc.alloc(t.conc.size()); rlx_bin_spec.alloc(t.bin_spec.size()); rlx_vol.alloc(size_t(o.nz));
+    // the domain's volume at each level (hor_dv_eval; the extent in y counts in 2-D as well)
+    std::vector<T> vol(size_t(o.nz));
+    const T x0 = T(o.x0), y0 = T(o.y0), z0 = T(o.z0), x1 = T(o.x1), y1 = T(o.y1), z1 = T(o.z1), dz = T(o.dz);
+    for (int k = 0; k < o.nz; ++k) vol[size_t(k)] = std::max(T(0), T((x1 - x0) * (y1 - y0) * (std::min(T((k + 1) * dz), z1) - std::max(T(k * dz), z0))));
+    HIPCHK(hipMemcpyAsync(rlx_specs.p, t.specs.data(), t.specs.size() * sizeof(rlx_spec<T>), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rlx_edges.p, t.edges.data(), t.edges.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rlx_conc.p, t.conc.data(), t.conc.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rlx_bin_spec.p, t.bin_spec.data(), t.bin_spec.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rlx_vol.p, vol.data(), vol.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    sync();                                                                              // (vol is a local)
+    rlx_count.alloc(rlx_m); rlx_create.alloc(rlx_m); rlx_off.alloc(rlx_m); rlx_mult.alloc(rlx_m);
+    rlx_tiles.alloc((rlx_m + SCAN_TILE - 1) / SCAN_TILE + 1); rlx_total.alloc(1);
+    rlx_lds_bytes = size_t(t.tot_bins) * sizeof(unsigned long long) + t.edges.size() * sizeof(T);
+  }
+  bool rlx_fires() const { return !rlx_tab.specs.empty() && rlx_k_end > rlx_k_first && rlx_stp_ctr % size_t(o.supstp_rlx) == 0; }
+  // census + plan + scan, queued on the stream; the count of newcomers stays on the device (rlx_total)
+  void rlx_census_and_plan()
+  {
+    const RlxTables<T> &t = rlx_tab;
+    if (rlx_any_fn) {         // a user's function is evaluated at every firing, as the reference does: rlx_bins calls, not one per droplet
+      // (no host wait of its own: the copy is ordered on the stream and rlx_conc_h lives until the next firing, past this step's read-back)
+      rlx_conc_h.resize(t.conc.size());
+      for (const rlx_spec<T> &sp : t.specs)
+        for (int b = 0; b < sp.n_bins; ++b) {
+          const lcx_distro_t &d = rlx_distros[size_t(&sp - t.specs.data())].distro;
+          rlx_conc_h[size_t(sp.bin0 + b)] = d.fn ? T(T(eval_distro_host(d, T(sp.log_rd_min + (b + 0.5) * sp.bin_size))) * sp.bin_size) : t.conc[size_t(sp.bin0 + b)];
+        }
+      HIPCHK(hipMemcpyAsync(rlx_conc.p, rlx_conc_h.data(), rlx_conc_h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    }
+    if (nphys && !dbg(LCX_DBG_RLX_GLOBAL_ATOMICS)) hskpng_sort();      // (the order that condensation / coalescence have just used; a no-op then)
+    {
+    Range r(this, "rlx_census");
+    HIPCHK(hipMemsetAsync(rlx_count.p, 0, rlx_m * sizeof(unsigned long long), st));
+    const T *kp = kpa_uniform ? (const T *)nullptr : (const T *)A.kpa.p;
+    if (nphys && dbg(LCX_DBG_RLX_GLOBAL_ATOMICS))
+      hipLaunchKernelGGL(k_rlx_census_global<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, (const rlx_spec<T> *)rlx_specs.p, int(t.specs.size()), (const T *)rlx_edges.p, o.nz,
+                         (const uint32_t *)ijk.p, (const n_t *)A.n.p, (const T *)A.rd3.p, kp, kpa_value, rlx_count.p);
+    else if (nphys) {
+      const int n_lev = rlx_k_end - rlx_k_first;
+      const uint32_t n_cols = uint32_t(ncell / size_t(o.nz));
+      // about two workgroups of sixteen waves per CU over the levels in use (k_rlx_census says why), a wave taking 64 columns per trip
+      const uint32_t want_chunks = std::max<uint32_t>(1u, 512u / uint32_t(n_lev));
+      const uint32_t cols_per_wg = std::max<uint32_t>(uint32_t(WAVE), (n_cols + want_chunks - 1) / want_chunks);
+      const uint32_t n_chunks = (n_cols + cols_per_wg - 1) / cols_per_wg;
+      hipLaunchKernelGGL(k_rlx_census<T>, dim3(unsigned(n_lev) * n_chunks), dim3(RLX_BS), rlx_lds_bytes, st, (const rlx_spec<T> *)rlx_specs.p, int(t.specs.size()),
+                         (const T *)rlx_edges.p, t.tot_bins, int(t.edges.size()), o.nz, rlx_k_first, n_lev, n_cols, cols_per_wg, (const uint32_t *)cell_start.p,
+                         (const uint32_t *)sid(), (const n_t *)A.n.p, (const T *)A.rd3.p, kp, kpa_value, rlx_count.p);
+    }
+    }
+    Range r(this, "rlx_plan");
+    const T dt_rlx = T(o.supstp_rlx * T(dt));                                             // particles_step.ipp:471
+    const T frac = std::min(T(dt_rlx / T(o.rlx_timescale)), T(1));
+    hipLaunchKernelGGL(k_rlx_plan<T>, dim3(nblk(rlx_m)), dim3(BS), 0, st, rlx_m, o.nz, (const rlx_spec<T> *)rlx_specs.p, (const int *)rlx_bin_spec.p, (const T *)rlx_conc.p,
+                       (const T *)rlx_vol.p, (const T *)rhod.p, o.aerosol_independent_of_rhod, (const unsigned long long *)rlx_count.p, T(0.1) /* config.hpp:33 */,
+                       rlx_n_per_bin, T(o.rlx_sd_per_bin), frac, rlx_create.p, rlx_mult.p);
+    const size_t tiles = (rlx_m + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(unsigned(tiles)), dim3(BS), 0, st, (const uint32_t *)rlx_create.p, rlx_off.p, rlx_tiles.p, rlx_m);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, rlx_tiles.p, tiles, rlx_total.p);
+  }
+  // the firing's one read-back, then the newcomers behind the storage extent
+  void rlx_create_new()
+  {
+    uint32_t n_new = 0;
+    read_back(&n_new, rlx_total.p, 1);
+    if (n_new == 0) return;
+    Range r(this, "rlx_create");
+    const size_t n_old = src_make_room(n_new);
+    const u01_src<T> r_i = rand_u01(n_new), r_rd = rand_u01(n_new), r_j = n_dims == 3 ? rand_u01(n_new) : u01_src<T>{nullptr, 0, 0};
+    hipLaunchKernelGGL(k_rlx_create<T>, dim3(nblk(rlx_m * size_t(rlx_n_per_bin))), dim3(BS), 0, st, rlx_m, rlx_n_per_bin, o.nz, (const uint32_t *)rlx_create.p,
+                       (const uint32_t *)rlx_off.p, (const uint32_t *)rlx_tiles.p, (const n_t *)rlx_mult.p, (const rlx_spec<T> *)rlx_specs.p, (const int *)rlx_bin_spec.p,
+                       (const T *)rlx_edges.p, r_i, r_rd, r_j, o.nx, n_dims == 3 ? o.ny : 0, n_old, ijk.p, A.rd3.p, A.kpa.p, A.n.p, A.vt.p);
+    src_finish_new(n_new, n_old, rlx_tab.specs[0].kappa);
+    for (const rlx_spec<T> &sp : rlx_tab.specs) if (kpa_uniform && sp.kappa != kpa_value) kpa_uniform = false;
+    release_replay_keep();
+  }
   void init_kernel()
   {                                                                                      // init_kernel.ipp:6-233
     std::vector<double> params = kernel_parameters_h;
@@ -2162,11 +2337,16 @@ struct Particles : IParticles {
     // neighbours take the plain sequence (move, append, post_copy), as a step with opts.rcyc does.
     const bool src_now = opts.src && src_box_on() && src_check_and_fires(opts);
     const bool src_plain = src_now && (o.src_type == 2 || distmem() || nphys == 0 || nphys + src_total_new(opts) > cap);
-    if (opts.rlx) throw lcx_error("libcloudph++: aerosol relaxation was switched off in opts_init");
+    if (opts.rlx && !o.rlx_switch) throw lcx_error("libcloudph++: aerosol relaxation was switched off in opts_init");
     adjust_timesteps(opts.dt);
+    // Relaxation (never together with a source in one object): a step in which it does not fire launches what it launches without
+    // opts.rlx.  A firing on a single device keeps the fused move like the simple source; short of room for the most it can create, or
+    // with neighbours, it takes the plain sequence.
+    const bool rlx_now = opts.rlx && rlx_fires();
+    const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
     last_async_coal = opts.coal != 0;
-    coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
+    coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
                                                        // substeps a used-up SD still takes part in the later ones and keeps its cell)
     hskpng_Tpr(opts.sedi || opts.coal || opts.cond);
     if (opts.sedi || opts.coal || opts.cond) hskpng_vterm(false);
@@ -2189,8 +2369,9 @@ struct Particles : IParticles {
     turb_adve_now = opts.turb_adve;
     // > 0 dimensions: advection + sedimentation + boundary + re-indexing in ONE pass over the positions; with a decomposed
     // domain the histogram is completed by the immigrants in migrate_finish
-    const bool fused = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain;
-    hold_big_list = fused && src_now;
+    const bool fused = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain;
+    hold_big_list = fused && (src_now || rlx_now);
+    if (rlx_now) rlx_census_and_plan();              // (on the cells of the step's start, before the move rewrites ijk)
     move(opts.adve, opts.sedi, opts.subs, true, fused);
     hold_big_list = false;
     adve_scheme = o.adve_scheme;
@@ -2206,7 +2387,17 @@ struct Particles : IParticles {
         list_big_from_hist();
       }
     }
+    if (rlx_now) {                                   // (as for the source: a newcomer lies strictly inside its cell and the domain)
+      const size_t n_old = nphys;
+      rlx_create_new();
+      if (fused) {
+        if (nphys > n_old)
+          hipLaunchKernelGGL(k_ijk_hist<T>, dim3(nblk(nphys - n_old)), dim3(BS), 0, st, n_old, nphys, g, A.n.p, A.x.p, A.y.p, A.z.p, ijk.p, cell_cnt.p, rnk(), 1, d_dead_p());
+        list_big_from_hist();
+      }
+    }
     if (opts.src) ++src_stp_ctr; else src_stp_ctr = 0;                                   // particles_step.ipp:476-479
+    if (opts.rlx) ++rlx_stp_ctr; else rlx_stp_ctr = 0;
     fused_pending = fused && distmem();
     n_before_unpack = nphys;
     if (fused && !distmem()) post_copy_after_fused_move(opts);
@@ -2369,6 +2560,9 @@ struct Particles : IParticles {
       }
       v.assign(1, c);
     }
+    else if (s == "raw_rlx_count") {               // aerosol relaxation: the last firing's census, count[bin][level] (empty before the first)
+      if (rlx_count.p && rlx_m) { auto h = d2h(rlx_count.p, rlx_m); v.assign(h.begin(), h.end()); }
+    }
     else if (s == "raw_n") { auto h = d2h(A.n.p, nphys); v.assign(h.begin(), h.end()); }
     else if (s == "raw_ijk") { auto h = d2h(ijk.p, nphys); v.assign(h.begin(), h.end()); }
     else if (s == "raw_sorted_id") {               // the cell-sorted order as the last sort left it (the shuffled order of the next coalescence, mostly)
@@ -2418,7 +2612,8 @@ struct Particles : IParticles {
       {"wp", ix_wp >= 0 ? A.ext[ix_wp].p : nullptr, ix_wp >= 0 ? npart : 0}, {"ssp", ix_ssp >= 0 ? A.ext[ix_ssp].p : nullptr, ix_ssp >= 0 ? npart : 0},
       {"incloud_time", ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, ix_ict >= 0 ? npart : 0},
       {"dot_ssp", ix_dot_ssp >= 0 ? A.ext[ix_dot_ssp].p : nullptr, ix_dot_ssp >= 0 ? npart : 0},
-      {"diss_rate", diss_rate.p, turb_any() ? ncell : 0}};
+      {"diss_rate", diss_rate.p, turb_any() ? ncell : 0},
+      {"raw_rlx_edges", rlx_edges.p, rlx_edges.p ? rlx_tab.edges.size() : 0}, {"raw_rlx_conc", rlx_conc.p, rlx_conc.p ? rlx_tab.conc.size() : 0}};
     for (const E &e : tab)
       if (s == e.nm) {
         *n = e.len;
@@ -2860,6 +3055,7 @@ void lcx_opts_init_default(lcx_opts_init_t *o)
   o->sstp_cond_adapt_drw2_eps = 1e-4; o->sstp_cond_adapt_drw2_max = 4; o->rc2_T = 10;
   o->adve_scheme = LCX_ADVE_IMPLICIT; o->RH_formula = LCX_RH_PV_CC;
   o->dev_id = -1; o->rd_min = -1; o->rd_max = -1; o->th_dry = 1; o->strict_fp = 0; o->cond_solver = 1;   /* (round 5: the API default, see lcx.h) */
+  o->rlx_timescale = 1; o->supstp_rlx = 1;                                                                /* opts_init.hpp: rlx_bins 0, rlx_sd_per_bin 0, no spectra */
 }
 void lcx_opts_default(lcx_opts_t *o)
 {
@@ -2878,6 +3074,19 @@ int lcx_create(const lcx_opts_init_t *oi, int real_kind, lcx_particles **out)
     else throw std::runtime_error("libcloudph++: real_kind must be 4 (float) or 8 (double)");
     *out = h.release();
   })
+}
+int lcx_rlx_layout(const lcx_opts_init_t *oi, int spectrum, double *edges_rd3, double *centre_conc, int *n_bins)
+{
+  try {                                              // (host only: no device is looked for or bound)
+    lcx::rlx_check_opts(*oi);
+    if (spectrum < 0 || spectrum >= oi->n_rlx_dry_distros) throw std::runtime_error("libcloudph++ (HIP): lcx_rlx_layout: no such entry of rlx_dry_distros");
+    const lcx::RlxTables<double> t = lcx::rlx_make_tables<double>(*oi);
+    const lcx::rlx_spec<double> &s = t.specs[size_t(spectrum)];
+    if (n_bins) *n_bins = s.n_bins;
+    if (edges_rd3) std::copy(t.edges.begin() + s.edge0, t.edges.begin() + s.edge0 + s.n_bins + 1, edges_rd3);
+    if (centre_conc) std::copy(t.conc.begin() + s.bin0, t.conc.begin() + s.bin0 + s.n_bins, centre_conc);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; } catch (...) { g_err = "libcloudph++: unknown error"; return 1; }
 }
 int lcx_create_multi(const lcx_opts_init_t *oi, int real_kind, lcx_particles **out)
 {

@@ -3083,6 +3083,163 @@ __global__ void __launch_bounds__(BS) k_src_match(const uint32_t *cells, uint32_
 template <class T> __global__ void k_fill_index_from(T *a, size_t n, T first) { size_t i = gid(); if (i < n) a[i] = first + T(i); }
 
 // ============================================================================================
+// aerosol relaxation (src/impl/sources_and_relaxation_of_SDs/particles_impl_rlx_dry_distros.ipp)
+// ============================================================================================
+// The reference takes, for every size bin of every relaxation spectrum, two filter passes over all super-droplets, a per-cell moment, a
+// sort by level and a reduction.  Here a firing is ONE pass (the census) into a table count[bin][level] of summed multiplicities for
+// all spectra and all bins at once, a plan with one thread per (bin, level), a scan of the plan and one launch that creates the
+// newcomers: none of the launches depends on rlx_bins.
+//
+// One relaxation spectrum as the kernels see it.  The bins of all spectra are numbered through (bin0 .. bin0 + n_bins); a spectrum's
+// n_bins + 1 edges (rd3, made on the host in real_t: the reference's own table) begin at edge0 = bin0 + its index.
+constexpr int RLX_MAX_BINS = 1024;      // = LCX_RLX_MAX_BINS (static_assert in lcx_core.hip): the census keeps count (8 B) and edge (real_t) of every bin in LDS,
+                                        // 16 KiB + 8 B per spectrum at the cap in double.  Not LDS sets the cap but the census' time: at 1024 bins it is
+                                        // within 0-3 % of the time at 64, at 2048 4 % and at 4096 12 % above (flushes: EXPERIMENTS.md 7.2)
+constexpr int RLX_BS = 1024;            // the census' workgroup: sixteen waves share one table, so that two workgroups fill a CU's wave slots at any table size
+template <class T> struct rlx_spec {
+  T kpa_min, kpa_max;                   // counted: kpa_min <= kappa < kpa_max
+  T log_rd_min, bin_size, inv_bin_size; // equal bins in ln rd
+  T kappa;                              // of what is created
+  int bin0, n_bins, edge0, k_lo, k_hi;  // relaxed levels: k_lo <= k < k_hi
+};
+// the bin of rd3 by comparison with the host's edges: guessed from the logarithm, corrected against the neighbouring edges (a
+// droplet ON an edge belongs to the upper bin; the loops end after one trip unless the logarithm was far off); -1: outside the bins
+template <class T> __device__ __forceinline__ int rlx_bin_of(const rlx_spec<T> &s, const T *e /* the spectrum's edges */, T r3)
+{
+  if (!(r3 >= e[0]) || !(r3 < e[s.n_bins])) return -1;
+  int b = int((log(r3) / T(3) - s.log_rd_min) * s.inv_bin_size);
+  b = b < 0 ? 0 : b > s.n_bins - 1 ? s.n_bins - 1 : b;
+  while (r3 < e[b]) --b;                // (e[0] <= r3 < e[n_bins]: both loops stay inside the table)
+  while (!(r3 < e[b + 1])) ++b;
+  return b;
+}
+// The census.  The flat cell index is (i * ny + j) * nz + k: a workgroup of RLX_BS threads owns level k_first + blockIdx.x % n_lev and
+// the columns [chunk * cols_per_wg, ...) and walks the cell-sorted segments cell_start[c] .. cell_start[c + 1] of its cells, one wave
+// per cell (after a re-ordering a segment's ids are contiguous in storage: 64 x 8 B per attribute).  All bins of the level live in
+// LDS, added to with LDS atomics on 64 bits (integer sums: exact and independent of the order); one flush per workgroup with 64-bit
+// global atomics, non-zero entries only.  The kernel is bound by the latency of its gathers, so what it needs is waves in flight
+// whatever the table's size: sixteen waves per table (workgroups of 256 threads ran 8 % slower at 1024 bins than at 64 and 2.5 x slower
+// at 4096, where two of them = eight waves were left per CU), and about two workgroups per CU in all, so that the flushes stay few against the droplets.
+// Levels that no spectrum relaxes are not visited at all.  The cells are those of the sorted order, i.e. of the START of
+// step_async (the reference's ijk is not refreshed before its relaxation either).  A dead super-droplet (n == 0) adds nothing.
+// LDS: tot_bins x 8 B + tot_edges x sizeof(T) (dynamic).  grid = n_lev * n_chunks.
+template <class T>
+__global__ void __launch_bounds__(RLX_BS)
+k_rlx_census(const rlx_spec<T> *specs, int n_spec, const T *edges, int tot_bins, int tot_edges, int nz, int k_first, int n_lev, uint32_t n_cols,
+             uint32_t cols_per_wg, const uint32_t *cell_start, const uint32_t *sorted_id, const n_t *n, const T *rd3, const T *kpa, T kpa_value,
+             unsigned long long *count)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned long long rlx_lds[];
+  unsigned long long *tab = rlx_lds;
+  T *e_s = reinterpret_cast<T *>(tab + tot_bins);
+  for (int b = threadIdx.x; b < tot_bins; b += RLX_BS) tab[b] = 0ull;
+  for (int b = threadIdx.x; b < tot_edges; b += RLX_BS) e_s[b] = edges[b];
+  __syncthreads();
+  const int k = k_first + int(blockIdx.x % unsigned(n_lev));
+  const uint32_t col0 = (blockIdx.x / unsigned(n_lev)) * cols_per_wg, col1 = col0 + cols_per_wg < n_cols ? col0 + cols_per_wg : n_cols;
+  // 64 columns per trip of a wave: every lane fetches one cell's segment bounds, then the wave takes the cells in turn
+  for (uint32_t base = col0 + wave_id() * WAVE; base < col1; base += RLX_BS) {
+    const uint32_t mycol = base + lane_id();
+    uint32_t s_l = 0, e_l = 0;
+    if (mycol < col1) { const size_t c = size_t(mycol) * nz + k; s_l = cell_start[c]; e_l = cell_start[c + 1]; }
+    const int n_here = int(col1 - base < uint32_t(WAVE) ? col1 - base : uint32_t(WAVE));
+    for (int w = 0; w < n_here; ++w) {
+      const uint32_t s = __shfl(s_l, w), e = __shfl(e_l, w);
+      for (uint32_t q = s + lane_id(); q < e; q += WAVE) {
+        const uint32_t id = sorted_id[q];
+        const n_t m = n[id];
+        if (m == 0) continue;
+        const T r3 = rd3[id], kp = kpa ? kpa[id] : kpa_value;
+        for (int sp = 0; sp < n_spec; ++sp) {
+          const rlx_spec<T> S = specs[sp];
+          if (k < S.k_lo || k >= S.k_hi || !(kp >= S.kpa_min) || !(kp < S.kpa_max)) continue;
+          const int b = rlx_bin_of(S, e_s + S.edge0, r3);
+          if (b >= 0) atomicAdd(&tab[S.bin0 + b], m);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < tot_bins; b += RLX_BS) {
+    const unsigned long long v = tab[b];
+    if (v) atomicAdd(&count[size_t(b) * nz + k], v);
+  }
+}
+// the census without the LDS table (LCX_DBG_RLX_GLOBAL_ATOMICS; measured 4.9 x slower, kept only as the tests' cross-check of the table): one pass in storage order, the cell from ijk (which
+// a step's move has not touched yet), a global 64-bit atomic per counted droplet
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_rlx_census_global(size_t n_phys, const rlx_spec<T> *specs, int n_spec, const T *edges, int nz, const uint32_t *ijk, const n_t *n, const T *rd3,
+                    const T *kpa, T kpa_value, unsigned long long *count)
+{
+  const size_t i = gid(); if (i >= n_phys) return;
+  const uint32_t c = ijk[i];
+  if (c == DEAD_CELL) return;
+  const n_t m = n[i];
+  if (m == 0) return;
+  const int k = int(c % uint32_t(nz));
+  const T r3 = rd3[i], kp = kpa ? kpa[i] : kpa_value;
+  for (int sp = 0; sp < n_spec; ++sp) {
+    const rlx_spec<T> S = specs[sp];
+    if (k < S.k_lo || k >= S.k_hi || !(kp >= S.kpa_min) || !(kp < S.kpa_max)) continue;
+    const int b = rlx_bin_of(S, edges + S.edge0, r3);
+    if (b >= 0) atomicAdd(&count[size_t(S.bin0 + b) * nz + k], m);
+  }
+}
+// The plan, one thread per (bin, level), e = bin * nz + k: the reference's expressions in its order of operations
+// (rlx_dry_distros.ipp:186-216,248-258).  conc: the spectrum at the bin's centre times the bin's width (STP); vol: the domain's volume at
+// the level; rhod: the FIRST column's profile, as the reference reads it.  create[e]: super-droplets to make, mult[e]: their multiplicity.
+template <class T>
+__global__ void k_rlx_plan(size_t m, int nz, const rlx_spec<T> *specs, const int *bin_spec, const T *conc, const T *vol, const T *rhod, int indep_rhod,
+                           const unsigned long long *count, T tolerance, int n_per_bin, T sd_per_bin, T frac, uint32_t *create, n_t *mult)
+{
+  const size_t e = gid(); if (e >= m) return;
+  const int b = int(e / size_t(nz)), k = int(e % size_t(nz));
+  const int k_lo = specs[bin_spec[b]].k_lo, k_hi = specs[bin_spec[b]].k_hi;
+  T expected = conc[b] * vol[k];
+  if (!indep_rhod) expected = expected * rhod[k] / cst<T>::rho_stp;
+  if (k < k_lo || k >= k_hi) expected = T(0);
+  T missing = expected - T(count[e]);
+  if (missing < T(0)) missing = T(0);
+  create[e] = expected > T(0) ? (missing / expected > tolerance ? uint32_t(n_per_bin) : 0u) : 0u;
+  mult[e] = n_t(missing / sd_per_bin * frac + T(0.5));
+}
+// largest real_t below a positive finite x
+__device__ __forceinline__ double rlx_below(double x) { return __longlong_as_double(__double_as_longlong(x) - 1); }
+__device__ __forceinline__ float rlx_below(float x) { return __int_as_float(__float_as_int(x) - 1); }
+// The newcomers, one thread per (bin, level, j < n_per_bin), appended behind n_old in that order (the reference's: spectra, bins,
+// levels).  off + tile_off: the exclusive scan of create.  i (and j) uniform over the whole level, ln rd uniform inside the bin
+// (rlx_dry_distros.ipp:267-296); rd3 is held inside [edge_b, edge_b+1) where the rounding of exp would put it onto or across an edge,
+// and the column inside the grid where real_t rounds u * nx up to nx.
+template <class T>
+__global__ void k_rlx_create(size_t m, int n_per_bin, int nz, const uint32_t *create, const uint32_t *off, const uint32_t *tile_off, const n_t *mult,
+                             const rlx_spec<T> *specs, const int *bin_spec, const T *edges, u01_src<T> r_i, u01_src<T> r_rd, u01_src<T> r_j, int nx, int ny,
+                             size_t n_old, uint32_t *ijk, T *rd3, T *kpa, n_t *n, T *vt)
+{
+  const size_t g = gid();
+  const size_t e = g / size_t(n_per_bin);
+  if (e >= m || create[e] == 0u) return;
+  const size_t q = size_t(off[e]) + tile_off[e / SCAN_TILE] + g % size_t(n_per_bin), p = n_old + q;
+  const int b = int(e / size_t(nz)), k = int(e % size_t(nz));
+  const rlx_spec<T> S = specs[bin_spec[b]];
+  const T lo = edges[S.edge0 + (b - S.bin0)], hi = edges[S.edge0 + (b - S.bin0) + 1];
+  const T u_i = r_i.arr ? r_i.arr[q] : philox::u01<T>(q, r_i.call, r_i.seed);
+  const T u_rd = r_rd.arr ? r_rd.arr[q] : philox::u01<T>(q, r_rd.call, r_rd.seed);
+  size_t i = size_t(u_i * T(nx)), j = 0;
+  if (i >= size_t(nx)) i = size_t(nx) - 1;
+  if (ny > 0) {
+    const T u_j = r_j.arr ? r_j.arr[q] : philox::u01<T>(q, r_j.call, r_j.seed);
+    j = size_t(u_j * T(ny));
+    if (j >= size_t(ny)) j = size_t(ny) - 1;
+  }
+  T r3 = exp(T(3) * (log(lo) / T(3) + u_rd * S.bin_size));
+  if (r3 < lo) r3 = lo;
+  if (!(r3 < hi)) r3 = rlx_below(hi);
+  ijk[p] = uint32_t((i * size_t(ny > 0 ? ny : 1) + j) * size_t(nz) + size_t(k));
+  rd3[p] = r3; kpa[p] = S.kappa; n[p] = mult[e]; vt[p] = T(-1);
+}
+
+// ============================================================================================
 // 1-D domain decomposition: migrant lists, pack, unpack (bcnd.ipp:160-205, pack.ipp:14-133, unpack.ipp:14-143)
 // ============================================================================================
 // stable list of ids with mig[i] == side (copy_if order): flags -> tile sums -> scan -> ids

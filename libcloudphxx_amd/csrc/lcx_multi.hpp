@@ -122,6 +122,9 @@ struct MultiParticles : IParticles {
         o.src_x0 = oi.src_x0 - bfr * oi.dx; o.src_x1 = oi.src_x1 - bfr * oi.dx;
         if (o.src_x1 <= o.x0 || o.src_x0 >= o.x1) o.src_x0 = o.src_x1 = 0;
         else { if (o.src_x0 < o.x0) o.src_x0 = o.x0; if (o.src_x1 > o.x1) o.src_x1 = o.x1; }
+        // aerosol relaxation: every slab relaxes on its own horizontal sums over its own x0 .. x1, with its share of the
+        // super-droplets per bin (distmem_opts.hpp:49, particles_multi_gpu_ctor.ipp:40) -- the result depends on the slab count
+        o.rlx_sd_per_bin = oi.rlx_sd_per_bin / D;
         const bool first = i == 0, last = i == D - 1;
         o.bcond_lft = first && !periodic ? 3 : 1;                                  // particles_multi_gpu_impl.ipp:158-179
         o.bcond_rgt = last && !periodic ? 3 : 1;

@@ -118,6 +118,7 @@ class dbg(enum.IntFlag):
     COND_PROBE = 1 << 26
     COND_NO_FUSED_SUBSTEPS = 1 << 27
     VTERM_INVALID_OWN_PASS = 1 << 28
+    RLX_GLOBAL_ATOMICS = 1 << 29
 
 
 class cond_kernel(enum.IntEnum):
@@ -162,6 +163,10 @@ class _dry_size_c(C.Structure):
                 ("sd_count", C.c_int)]
 
 
+class _rlx_distro_c(C.Structure):
+    _fields_ = [("distro", _distro_c), ("kappa_min", C.c_double), ("kappa_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
 class _opts_init_c(C.Structure):
     _fields_ = [
         ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
@@ -196,6 +201,8 @@ class _opts_init_c(C.Structure):
         ("dbg_flags", C.c_uint), ("dbg_cond_budget", C.c_int), ("dbg_pack_delay_us", C.c_int),
         ("src_x0", C.c_double), ("src_y0", C.c_double), ("src_z0", C.c_double),
         ("src_x1", C.c_double), ("src_y1", C.c_double), ("src_z1", C.c_double),
+        ("rlx_bins", C.c_int), ("supstp_rlx", C.c_int), ("rlx_sd_per_bin", C.c_double), ("rlx_timescale", C.c_double),
+        ("rlx_dry_distros", C.POINTER(_rlx_distro_c)), ("n_rlx_dry_distros", C.c_int),
     ]
 
 
@@ -318,11 +325,12 @@ class opts_init_t:
         self.diag_incloud_time = False
         # box of the aerosol source (src_type simple / matching; the spectra are in opts_t)
         self.src_x0 = self.src_y0 = self.src_z0 = self.src_x1 = self.src_y1 = self.src_z1 = 0.
-        # fields of the parts that are outside this library (chemistry, relaxation): kept so that scripts written
-        # for the reference can set and print them; the matching switches make the constructor throw
-        self.chem_rho = 0.
+        # aerosol relaxation (rlx_switch, opts.rlx): {kappa: [spectrum at STP, [kappa_min, kappa_max], [z_min, z_max]]}
         self.rlx_dry_distros = {}
         self.rlx_bins, self.rlx_timescale, self.rlx_sd_per_bin, self.supstp_rlx = 0, 1., 0., 1
+        # fields of the parts that are outside this library (chemistry): kept so that scripts written
+        # for the reference can set and print them; the matching switches make the constructor throw
+        self.chem_rho = 0.
         # extensions (include/lcx.h)
         self.n_x_tot = 0
         self.n_x_bfr = 0
@@ -341,7 +349,7 @@ class opts_init_t:
     def _to_c(self, keep):
         c = _opts_init_c()
         special = {"kernel_parameters", "n_kernel_parameters", "w_LS", "n_w_LS", "SGS_mix_len", "n_SGS_mix_len", "aerosol_conc_factor",
-                   "n_aerosol_conc_factor", "dry_distros", "n_dry_distros", "dry_sizes", "n_dry_sizes"}
+                   "n_aerosol_conc_factor", "dry_distros", "n_dry_distros", "dry_sizes", "n_dry_sizes", "rlx_dry_distros", "n_rlx_dry_distros"}
         for name, ctype in _opts_init_c._fields_:
             if name in special:
                 continue
@@ -372,7 +380,38 @@ class opts_init_t:
         keep.append(sarr)
         c.dry_sizes = C.cast(sarr, C.POINTER(_dry_size_c))
         c.n_dry_sizes = len(flat)
+        # rlx_dry_distros: std::map order = sorted by kappa (null pointer, zero count when empty)
+        kappas = sorted(self.rlx_dry_distros.keys())
+        if kappas:
+            rarr = (_rlx_distro_c * len(kappas))()
+            for i, k in enumerate(kappas):
+                fun, kappa_rng, z_rng = self.rlx_dry_distros[k]
+                _fill_distro(rarr[i].distro, (k, 0.), fun, keep)
+                rarr[i].kappa_min, rarr[i].kappa_max = float(kappa_rng[0]), float(kappa_rng[1])
+                rarr[i].z_min, rarr[i].z_max = float(z_rng[0]), float(z_rng[1])
+            keep.append(rarr)
+            c.rlx_dry_distros = C.cast(rarr, C.POINTER(_rlx_distro_c))
+            c.n_rlx_dry_distros = len(kappas)
         return c
+
+
+def rlx_layout(opts_init, spectrum=0, lib=None):
+    """Size bins of aerosol relaxation for entry `spectrum` (in kappa order) of opts_init.rlx_dry_distros as an object in double lays
+    them out (lcx_rlx_layout, include/lcx_rlx.h; needs no GPU): (bin edges in rd3 [n_bins + 1], expected STP concentration per bin [n_bins])."""
+    lib = lib if lib is not None else _lib.load()
+    keep = []
+    c = opts_init._to_c(keep)
+    n = C.c_int()
+
+    def chk(rc):
+        if rc != 0:
+            lib.lcx_last_error.restype = C.c_char_p
+            raise RuntimeError(lib.lcx_last_error().decode())
+    chk(lib.lcx_rlx_layout(C.byref(c), C.c_int(spectrum), None, None, C.byref(n)))
+    edges, conc = np.zeros(n.value + 1), np.zeros(n.value)
+    chk(lib.lcx_rlx_layout(C.byref(c), C.c_int(spectrum), edges.ctypes.data_as(C.POINTER(C.c_double)),
+                           conc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+    return edges, conc
 
 
 class opts_t:

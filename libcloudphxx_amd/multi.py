@@ -50,6 +50,9 @@ def distmem_opts(opts_init, rank, size, self_ring=False):
     if int(opts_init.src_type) != 0:
         raise RuntimeError("libcloudph++: aerosol sources: use the multi-device object (factory(backend_t.multi_HIP, ...)); "
                            "the one-process-per-GPU path does not carry them")
+    if opts_init.rlx_switch:
+        raise RuntimeError("libcloudph++: aerosol relaxation: use the multi-device object (factory(backend_t.multi_HIP, ...)); "
+                           "the one-process-per-GPU path does not carry it")
     oi = copy.copy(opts_init)
     oi.dry_distros = dict(opts_init.dry_distros)
     n_x_bfr = rank * get_dev_nx(opts_init.nx, 0, size)
