@@ -76,11 +76,13 @@ typedef struct { double kappa, rd_insol, radius, conc; int sd_count; } lcx_dry_s
 typedef struct { lcx_distro_t distro; double kappa_min, kappa_max, z_min, z_max; } lcx_rlx_distro_t;
 
 /* POD mirror of opts_init_t<real_t> (opts_init.hpp:29-253); same field names and defaults.
- * Fields of sub-systems that are out of scope (chemistry, ice) are kept so that a
- * caller's settings are checked, not silently dropped: lcx_create() fails if one of them is
- * switched on.  The aerosol source (src_type simple / matching, the box src_x0 .. src_z1 here,
- * the spectra in lcx_opts_t) and aerosol relaxation (rlx_switch, the rlx_* fields at the end) are built;
- * the two together in one object are refused. */
+ * Fields of the sub-system that is out of scope (ice) are kept so that a
+ * caller's settings are checked, not silently dropped: lcx_create() fails if it is
+ * switched on.  Aqueous chemistry (chem_switch, sstp_chem, chem_rho at the end; the entries that
+ * take the ambient trace gases are in include/lcx_chem.h) is built for a single device, without
+ * source and relaxation, as in the reference.  The aerosol source (src_type simple / matching, the
+ * box src_x0 .. src_z1 here, the spectra in lcx_opts_t) and aerosol relaxation (rlx_switch, the
+ * rlx_* fields at the end) are built; the two together in one object are refused. */
 typedef struct {
   int nx, ny, nz;
   double dx, dy, dz, dt;
@@ -169,6 +171,9 @@ typedef struct {
   double rlx_sd_per_bin, rlx_timescale;
   const lcx_rlx_distro_t *rlx_dry_distros;                  /* sorted by kappa like std::map */
   int n_rlx_dry_distros;
+  /* aqueous chemistry (chem_switch; opts_init.hpp: chem_rho 0): density of the dry aerosol [kg / m3], from which the initial NH4HSO4
+   * masses and the growth of the dry radius by the sulfate produced are taken; must be > 0 with chem_switch */
+  double chem_rho;
 } lcx_opts_init_t;
 #define LCX_RLX_MAX_BINS 1024
 
@@ -343,6 +348,7 @@ int lcx_outbuf(lcx_particles *, const void **data, size_t *n);
  * out == NULL to query the length */
 int lcx_get_attr(lcx_particles *, const char *name, void *out, size_t cap, size_t *n);
 int lcx_diag_puddle(lcx_particles *, double out[LCX_OUT_COUNT]);   /* particles_diag.ipp:411-421 */
+/* (aqueous chemistry -- init / sync_in / step_cond / step_sync with the ambient trace gases, diag_chem: include/lcx_chem.h) */
 
 /* ---- introspection / parity hooks (no reference counterpart; used by tests and bench) ---- */
 int lcx_n_part(lcx_particles *, size_t *n);

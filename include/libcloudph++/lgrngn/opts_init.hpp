@@ -2,9 +2,9 @@
 // (reference: lgrngn/opts_init.hpp:29-253), written with default member initialisers.
 // Everything is forwarded to lcx_opts_init_t (include/lcx.h).  Served: per-cell and per-particle condensation
 // substepping (exact_sstp_cond, sstp_cond_mix, adaptive_sstp_cond, sstp_cond_act), the SGS turbulence switches
-// (turb_adve / turb_cond / turb_coal), all initialisation modes, pred_corr advection, open side walls.  Switches of
-// sub-systems outside the accelerated path (chemistry, ice, aerosol sources, relaxation) make the constructor throw
-// instead of being ignored.
+// (turb_adve / turb_cond / turb_coal), all initialisation modes, pred_corr advection, open side walls, the aerosol source,
+// aerosol relaxation and aqueous chemistry (chem_switch, chem_rho, sstp_chem).  The switch of the sub-system outside the
+// accelerated path (ice) makes the constructor throw instead of being ignored.
 #pragma once
 #include "kernel.hpp"
 #include "terminal_velocity.hpp"

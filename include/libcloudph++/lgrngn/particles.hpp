@@ -14,6 +14,7 @@
 #include "arrinfo.hpp"
 #include "backend.hpp"
 #include "../../lcx.h"
+#include "../../lcx_chem.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -55,7 +56,7 @@ namespace libcloudphxx { namespace lgrngn {
     virtual void diag_vp_mom(const int &) { assert(false); }
     virtual void diag_wp_mom(const int &) { assert(false); }
     virtual void diag_water_cons() { assert(false); }
-    // diagnostics of the parts outside this library (chemistry, ice): declared for source compatibility, never served
+    // diagnostics of the part outside this library (ice) are declared for source compatibility, never served; diag_chem is overridden below
     virtual void diag_chem(const enum common::chem::chem_species_t &) { assert(false); }
     virtual void diag_ice() { assert(false); }
     virtual void diag_ice_cons() { assert(false); }
@@ -93,6 +94,21 @@ namespace libcloudphxx { namespace lgrngn {
       explicit carr(const arrinfo_t<real_t> &x) : null(x.is_null())
       { a.data = const_cast<void *>(static_cast<const void *>(x.data)); a.strides = x.strides; a.on_device = x.on_device ? 1 : 0; }
       const lcx_arrinfo_t *ptr() const { return null ? nullptr : &a; }
+    };
+    // the reference's ambient_chem map as the six pointers of include/lcx_chem.h (a species that the map lacks: a null entry)
+    template <typename real_t> struct cchem
+    {
+      lcx_arrinfo_t a[6]; const lcx_arrinfo_t *p[6];
+      template <class map_t> explicit cchem(const map_t &m)
+      {
+        for (int i = 0; i < 6; ++i) p[i] = nullptr;
+        for (const auto &kv : m) {
+          const int i = int(kv.first);
+          if (i < 0 || i >= 6 || kv.second.is_null()) continue;
+          a[i].data = const_cast<void *>(static_cast<const void *>(kv.second.data)); a[i].strides = kv.second.strides; a[i].on_device = kv.second.on_device ? 1 : 0;
+          p[i] = &a[i];
+        }
+      }
     };
   }
 
@@ -143,6 +159,7 @@ namespace libcloudphxx { namespace lgrngn {
       c.n_x_tot = n_x_tot; c.strict_fp = o.strict_fp; c.cond_solver = o.cond_solver; c.reorder_every = o.reorder_every; c.stream_ordered = o.stream_ordered;
       c.dbg_flags = o.dbg_flags;
       c.n_x_bfr = o.n_x_bfr; c.bcond_lft = o.bcond_lft; c.bcond_rgt = o.bcond_rgt;
+      c.chem_rho = o.chem_rho;
       c.src_x0 = o.src_x0; c.src_y0 = o.src_y0; c.src_z0 = o.src_z0; c.src_x1 = o.src_x1; c.src_y1 = o.src_y1; c.src_z1 = o.src_z1;
       // std::map iterates in (kappa, rd_insol) order, which is the order the library expects
       std::vector<lcx_distro_t> dd;
@@ -177,23 +194,26 @@ namespace libcloudphxx { namespace lgrngn {
     void init(const arr th, const arr rv, const arr rhod, const arr p = arr(), const arr courant_x = arr(), const arr courant_y = arr(),
               const arr courant_z = arr(), const cchem_t ambient_chem = cchem_t()) override
     {
-      if (!ambient_chem.empty()) throw std::runtime_error("libcloudph++: chemistry was switched off and ambient_chem is not empty");
       detail::carr<real_t> a(th), b(rv), c(rhod), d(p), e(courant_x), f(courant_y), g(courant_z);
-      detail::lcx_check(lcx_init(pimpl->h, a.ptr(), b.ptr(), c.ptr(), d.ptr(), e.ptr(), f.ptr(), g.ptr()));
+      if (ambient_chem.empty()) { detail::lcx_check(lcx_init(pimpl->h, a.ptr(), b.ptr(), c.ptr(), d.ptr(), e.ptr(), f.ptr(), g.ptr())); return; }
+      detail::cchem<real_t> ch(ambient_chem);
+      detail::lcx_check(lcx_init_chem(pimpl->h, a.ptr(), b.ptr(), c.ptr(), d.ptr(), e.ptr(), f.ptr(), g.ptr(), ch.p));
     }
     void sync_in(arr th, arr rv, const arr rhod = arr(), const arr courant_x = arr(), const arr courant_y = arr(), const arr courant_z = arr(),
                  const arr diss_rate = arr(), chem_t ambient_chem = chem_t()) override
     {
-      if (!ambient_chem.empty()) throw std::runtime_error("libcloudph++: chemistry was switched off and ambient_chem is not empty");
       detail::carr<real_t> a(th), b(rv), c(rhod), e(courant_x), f(courant_y), g(courant_z), d(diss_rate);
-      detail::lcx_check(lcx_sync_in(pimpl->h, a.ptr(), b.ptr(), c.ptr(), e.ptr(), f.ptr(), g.ptr(), d.ptr()));
+      if (ambient_chem.empty()) { detail::lcx_check(lcx_sync_in(pimpl->h, a.ptr(), b.ptr(), c.ptr(), e.ptr(), f.ptr(), g.ptr(), d.ptr())); return; }
+      detail::cchem<real_t> ch(ambient_chem);
+      detail::lcx_check(lcx_sync_in_chem(pimpl->h, a.ptr(), b.ptr(), c.ptr(), e.ptr(), f.ptr(), g.ptr(), d.ptr(), ch.p));
     }
     void step_cond(const opts_t<real_t> &opts, arr th, arr rv, chem_t ambient_chem = chem_t()) override
     {
-      (void)ambient_chem;
       const lcx_opts_t oc = conv(opts);
       detail::carr<real_t> a(th), b(rv);
-      detail::lcx_check(lcx_step_cond(pimpl->h, &oc, a.ptr(), b.ptr()));
+      if (ambient_chem.empty()) { detail::lcx_check(lcx_step_cond(pimpl->h, &oc, a.ptr(), b.ptr())); return; }
+      detail::cchem<real_t> ch(ambient_chem);
+      detail::lcx_check(lcx_step_cond_chem(pimpl->h, &oc, a.ptr(), b.ptr(), ch.p));
     }
     void step_sync(const opts_t<real_t> &opts, arr th, arr rv, const arr rhod = arr(), const arr courant_x = arr(), const arr courant_y = arr(),
                    const arr courant_z = arr(), const arr diss_rate = arr(), chem_t ambient_chem = chem_t()) override
@@ -222,6 +242,7 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_step_async(pimpl->h, &oc));
     }
 
+    void diag_chem(const enum common::chem::chem_species_t &c) override { detail::lcx_check(lcx_diag_chem(pimpl->h, int(c))); }
     void diag_sd_conc() override { detail::lcx_check(lcx_diag_sd_conc(pimpl->h)); }
     void diag_pressure() override { detail::lcx_check(lcx_diag_pressure(pimpl->h)); }
     void diag_temperature() override { detail::lcx_check(lcx_diag_temperature(pimpl->h)); }

@@ -23,6 +23,7 @@
 #include <atomic>
 #include "../../include/lcx.h"
 #include "../../include/lcx_rlx.h"
+#include "../../include/lcx_chem.h"
 #include "lcx_kernels.hpp"
 #include "lcx_pool.hpp"
 
@@ -120,6 +121,11 @@ struct IParticles {
   virtual void outbuf(const void **data, size_t *n) = 0;
   virtual void get_attr(const char *name, void *out, size_t cap, size_t *n) = 0;
   virtual void diag_puddle(double *out) = 0;
+  // aqueous chemistry (include/lcx_chem.h): the six ambient arrays of an lcx_*_chem entry are handed over here for the duration of the
+  // call (nullptr: an entry without them)
+  const lcx_arrinfo_t *const *chem_arg = nullptr;
+  virtual bool chem_on() const { return false; }
+  virtual void diag_chem(int) { throw std::runtime_error("libcloudph++: chemistry is switched off in opts_init, but diag_chem was called"); }
   virtual size_t n_part() = 0;
   virtual size_t n_cell() = 0;
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
@@ -287,6 +293,10 @@ struct Particles : IParticles {
   DevBuf<T> pp_dlt[4], pp_rw3s, pp_dst_rv, pp_dst_th;
   int ix_up = -1, ix_vp = -1, ix_wp = -1, ix_ssp = -1, ix_dot_ssp = -1;
   int ix_tag = -1;                    // LCX_DBG_TAG: a persistent tag per super-droplet (parity tests match droplets across re-orderings by it)
+  // aqueous chemistry (opts_init.chem_switch): masses A.ext[ix_chem + species], six ambient mixing ratios per cell
+  int ix_chem = -1, ix_chem_V = -1, ix_chem_flag = -1, sstp_chem = 1;
+  DevBuf<T> amb[CH_GAS], amb_tmp[CH_GAS], chem_delta[CH_GAS]; DevBuf<chem_cell<T>> chem_cc; DevBuf<chem_cell<double>> chem_ccd; DevBuf<n_t> chem_n_before; DevBuf<double> puddle_chem, puddle_chem_partial;
+  bool chem_on() const override { return o.chem_switch != 0; }
   int ix_ict = -1;                    // opts_init.diag_incloud_time: time spent activated, travels with the SD (particles_impl.ipp:475-476)
   std::vector<double> SGS_mix_len_h; DevBuf<T> SGS_mix_len, diss_rate, tau_cell, tau_rlx;
   bool turb() const { return o.turb_adve_switch || o.turb_cond_switch; }
@@ -349,8 +359,16 @@ struct Particles : IParticles {
   explicit Particles(const lcx_opts_init_t &oi) : o(oi)
   {
     // (relaxation is built, a source is built, the two in one object are not: DESIGN.md section 8)
-    if (oi.chem_switch || oi.ice_switch || (oi.rlx_switch && oi.src_type))
+    if (oi.ice_switch || (oi.rlx_switch && oi.src_type))
       throw lcx_error("libcloudph++: option outside the accelerated hot path (chem/ice/rlx)");
+    if (oi.chem_switch) {                                                            // init_sanity_check.ipp:57-67,131-143
+      if (oi.src_type != 0) throw lcx_error("libcloudph++: chemistry and aerosol source are not compatible");
+      if (oi.rlx_switch) throw lcx_error("libcloudph++: CCN relaxation does not work with chemistry");
+      if (oi.n_dry_distros > 1) throw lcx_error("libcloudph++: chemistry and multiple kappa distributions are not compatible");
+      if (oi.bcond_lft == 1 || oi.bcond_rgt == 1) throw lcx_error("libcloudph++: chemistry is not compatible with MPI");
+      if (!(oi.chem_rho > 0)) throw lcx_error("libcloudph++: chem_switch is set, but opts_init.chem_rho <= 0");      // (the reference asserts)
+      if (oi.sstp_chem < 1) throw lcx_error("libcloudph++: opts_init.sstp_chem needs to be greater than 0");
+    }
     if (oi.rlx_switch) {
       rlx_check_opts(oi);
       rlx_distros.assign(oi.rlx_dry_distros, oi.rlx_dry_distros + oi.n_rlx_dry_distros);
@@ -385,6 +403,8 @@ struct Particles : IParticles {
     if (oi.turb_cond_switch) { if (ix_wp < 0) ix_wp = n_ext++; ix_ssp = n_ext++; ix_dot_ssp = n_ext++; }
     if (oi.diag_incloud_time) ix_ict = n_ext++;
     if (dbg(LCX_DBG_TAG)) ix_tag = n_ext++;
+    // aqueous chemistry: the eight masses, and the volume and flag of the last substep, travel with the SD like the rest
+    if (oi.chem_switch) { ix_chem = n_ext; n_ext += CH_ALL; ix_chem_V = n_ext++; ix_chem_flag = n_ext++; sstp_chem = oi.sstp_chem; }
     SGS_mix_len_h.assign(oi.SGS_mix_len, oi.SGS_mix_len + oi.n_SGS_mix_len);
     o.SGS_mix_len = nullptr;
     pure_const_multi = (oi.sd_conc == 0) && (oi.sd_const_multi > 0 || oi.n_dry_sizes > 0);
@@ -424,6 +444,13 @@ struct Particles : IParticles {
     if (distmem()) alloc_mig();
     if (o.src_type && n_dims >= 2) list_src_cells();
     if (o.rlx_switch) rlx_alloc();
+    if (o.chem_switch) {
+      for (int e = ix_chem; e < ix_chem + CH_ALL + 2; ++e) HIPCHK(hipMemsetAsync(A.ext[e].p, 0, cap * sizeof(T), st));
+      for (int gs = 0; gs < CH_GAS; ++gs) { amb[gs].alloc_zero(ncell, st); if (o.sstp_chem > 1) amb_tmp[gs].alloc_zero(ncell, st); }
+      chem_cc.alloc(ncell);
+      if (sizeof(T) != sizeof(double)) chem_ccd.alloc(ncell);      // (a float object's H+ root is searched in double, k_chem)
+      puddle_chem.alloc_zero(CH_ALL, st);
+    }
   }
   ~Particles() override
   {
@@ -630,7 +657,8 @@ struct Particles : IParticles {
       // (more fields than planned for: wait, drain what the area still holds for the caller, start over)
       if (h.used) { flush_host_in(); sync(); if (&h == &hstage_out) finish_sync_out(); h.used = 0; }
       if (n > h.cap / sizeof(T)) {
-        const size_t want = std::max(n, &h == &hstage_in ? 4 * ncell + n_cx + n_cy + n_cz : 2 * ncell) * sizeof(T);
+        const size_t n_gas = o.chem_switch ? size_t(CH_GAS) * ncell : 0;
+        const size_t want = std::max(n, &h == &hstage_in ? 4 * ncell + n_cx + n_cy + n_cz + n_gas : 2 * ncell + n_gas) * sizeof(T);
         if (h.p) HIPCHK(hipHostFree(h.p));
         h.p = nullptr; h.cap = 0;
         HIPCHK(hipHostMalloc(&h.p, want, hipHostMallocDefault));
@@ -1569,6 +1597,7 @@ struct Particles : IParticles {
     sstp_cond = dt_ > 0 && o.sstp_cond > 1 ? int(std::ceil(o.sstp_cond * dt_ / o.dt)) : o.sstp_cond;
     sstp_cond_act = dt_ > 0 && o.sstp_cond_act > 1 ? int(std::ceil(o.sstp_cond_act * dt_ / o.dt)) : o.sstp_cond_act;
     sstp_coal = dt_ > 0 && o.sstp_coal > 1 ? int(std::ceil(o.sstp_coal * dt_ / o.dt)) : o.sstp_coal;
+    sstp_chem = dt_ > 0 && o.sstp_chem > 1 ? int(std::ceil(o.sstp_chem * dt_ / o.dt)) : o.sstp_chem;
     dt = dt_ > 0 ? dt_ : o.dt;
   }
 
@@ -1590,7 +1619,7 @@ struct Particles : IParticles {
     const bool onishi = o.kernel == LCX_KERNEL_ONISHI_HALL || o.kernel == LCX_KERNEL_ONISHI_HALL_DAVIS_NO_WAALS;
     // diss == nullptr stands for the reference's constant-zero dissipation rate when opts.turb_coal is off (coal.ipp:392-403,439-451)
     coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
-    const bool kappa_pass = o.n_dry_distros + n_size_keys > 1;
+    const bool kappa_pass = o.n_dry_distros + n_size_keys > 1, chem_pass = o.chem_switch != 0;
     auto launch = [&](auto kern, bool need_col = true) {
       hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
                          A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
@@ -1599,10 +1628,12 @@ struct Particles : IParticles {
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
     if (onishi) launch(k_coal<T, true>);
     // (the production kernel writes the collision record only for the kappa pass: nothing else reads it outside a replayed run)
-    else if (tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead) launch(k_coal<T, false, true>, kappa_pass);
+    else if (tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead) launch(k_coal<T, false, true>, kappa_pass || chem_pass);
     else launch(k_coal<T, false>);
     if (kappa_pass)
       hipLaunchKernelGGL(k_coal_kappa<T>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sid(), col.p, A.kpa.p, A.rd3.p);
+    if (chem_pass)                                                                       // coal.ipp:458-480
+      hipLaunchKernelGGL(k_coal_chem<T>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sid(), col.p, chem_ptrs());
   }
 
   // ------------------------------------------------------------------------------------------
@@ -2214,6 +2245,7 @@ struct Particles : IParticles {
   void init(const lcx_arrinfo_t *th_, const lcx_arrinfo_t *rv_, const lcx_arrinfo_t *rhod_, const lcx_arrinfo_t *p_,
             const lcx_arrinfo_t *cx, const lcx_arrinfo_t *cy, const lcx_arrinfo_t *cz) override
   {
+    if (!init_called) chem_check_arg();
     sanity_init(th_, rv_, rhod_, p_, cx, cy, cz);
     in_init = true;
     struct Leave { bool &f; ~Leave() { f = false; } } leave{in_init};
@@ -2230,6 +2262,7 @@ struct Particles : IParticles {
     if (!conc_factor_h.empty()) { std::vector<T> h(conc_factor_h.begin(), conc_factor_h.end()); conc_factor.alloc(h.size()); h2d(conc_factor.p, h.data(), h.size() * sizeof(T)); }
     sync_in_arr(th_, th, ncell, 0, 0, 0); sync_in_arr(rv_, rv, ncell, 0, 0, 0); sync_in_arr(rhod_, rhod, ncell, 0, 0, 0);
     sync_in_arr(p_, p, ncell, 0, 0, 0);
+    if (o.chem_switch) chem_sync_in();
     sync_in_arr(cx, courant_x, n_cx, 1, 0, 0, halo); sync_in_arr(cy, courant_y, n_cy, 0, 1, 0, halo); sync_in_arr(cz, courant_z, n_cz, 0, 0, 1, halo);
     flush_sync_jobs(); flush_host_in();
     if (n_dims > 0)
@@ -2248,6 +2281,7 @@ struct Particles : IParticles {
     }
     if (ix_tag >= 0 && nphys) hipLaunchKernelGGL(k_fill_index<T>, dim3(nblk(nphys)), dim3(BS), 0, st, A.ext[ix_tag].p, nphys);
     tag_next = nphys;
+    if (o.chem_switch) { chem_init_masses(nphys); sstp_save_chem(); }                    // particles_init.ipp: init_chem_aq, init_percell_sstp_chem
     hskpng_vterm(true);
     hskpng_approximate_rc2_invalid();                                                    // particles_init.ipp:116-117
     sstp_save();
@@ -2255,6 +2289,79 @@ struct Particles : IParticles {
     hskpng_count();
     if (!B.n.p) alloc_attrs(B);      // the compaction target: allocated here, not inside the first step that compacts (GBs of hipMalloc)
     sync();
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // aqueous chemistry (particles_step.ipp:269-327, src/impl/chemistry/)
+  // ------------------------------------------------------------------------------------------
+  static bool chem_arg_given(const lcx_arrinfo_t *const *a)
+  { if (a) for (int gs = 0; gs < CH_GAS; ++gs) if (!is_null(a[gs])) return true; return false; }
+  // init_sanity_check.ipp:51-55, particles_step.ipp:66-70
+  void chem_check_arg(bool needed = true) const
+  {
+    bool all = chem_arg != nullptr;
+    for (int gs = 0; all && gs < CH_GAS; ++gs) if (is_null(chem_arg[gs])) all = false;
+    if (o.chem_switch && needed && !all) throw lcx_error("libcloudph++: chemistry was not switched off and ambient_chem is empty");
+    if (!o.chem_switch && chem_arg_given(chem_arg)) throw lcx_error("libcloudph++: chemistry was switched off and ambient_chem is not empty");
+  }
+  chem_mass_ptrs<T> chem_ptrs() { chem_mass_ptrs<T> c; for (int sp = 0; sp < CH_ALL; ++sp) c.m[sp] = A.ext[ix_chem + sp].p; return c; }
+  void chem_init_masses(size_t n)
+  {                                                                                      // init_chem.ipp:176-223
+    if (!n) return;
+    hipLaunchKernelGGL(k_chem_init<T>, dim3(nblk(n)), dim3(BS), 0, st, n, A.rd3.p, T(o.chem_rho), chem_ptrs());
+    HIPCHK(hipMemsetAsync(A.ext[ix_chem_V].p, 0, n * sizeof(T), st)); HIPCHK(hipMemsetAsync(A.ext[ix_chem_flag].p, 0, n * sizeof(T), st));
+  }
+  void sstp_save_chem()
+  {                                                                                      // sstp_chem.ipp:14-33
+    if (o.sstp_chem <= 1) return;
+    for (int gs = 0; gs < CH_GAS; ++gs) HIPCHK(hipMemcpyAsync(amb_tmp[gs].p, amb[gs].p, ncell * sizeof(T), hipMemcpyDeviceToDevice, st));
+  }
+  void chem_sync_in() { for (int gs = 0; gs < CH_GAS; ++gs) sync_in_arr(chem_arg[gs], amb[gs], ncell, 0, 0, 0); }
+  // sstp_chem substeps: one cell pass for the step, then per substep one launch over the droplets and (chem_dsl) one wave per cell
+  void chem_step(const lcx_opts_t &opts)
+  {
+    hskpng_sort();
+    Range r(this, "chem");
+    const bool dsl = opts.chem_dsl != 0;
+    // (without rhod in sync_in the reference substeps the first five gases only, sstp_chem.ipp:69: kept)
+    const int n_sstp = dsl && o.sstp_chem > 1 ? (var_rho ? int(CH_GAS) : int(CH_GAS) - 1) : 0;
+    chem_fields<T> f;
+    for (int gs = 0; gs < CH_GAS; ++gs) { f.amb[gs] = amb[gs].p; f.tmp[gs] = amb_tmp[gs].p; }
+    hipLaunchKernelGGL(k_chem_cellpre<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, Tk.p, chem_cc.p, chem_ccd.p, f, n_sstp, T(sstp_chem));
+    chem_args<T> a{};
+    a.n_part = npart; a.sorted_id = sid(); a.sorted_ijk = sijk(); a.n = A.n.p; a.rw2 = A.rw2.p; a.rd3 = A.rd3.p;
+    for (int sp = 0; sp < CH_ALL; ++sp) a.m[sp] = A.ext[ix_chem + sp].p;
+    a.V_out = A.ext[ix_chem_V].p; a.flag_out = A.ext[ix_chem_flag].p;
+    a.cc = chem_cc.p; a.ccd = chem_ccd.p; a.Tk = Tk.p; a.rhod = rhod.p;
+    chem_fin_args<T> fin{};
+    fin.n_cell = ncell; fin.cell_start = cell_start.p; fin.f = f; fin.dv = dv.p; fin.rhod = rhod.p; fin.henry = 1; fin.n_sstp = n_sstp; fin.sstp = T(sstp_chem);
+    for (int gs = 0; gs < CH_GAS; ++gs) {
+      if (dsl) chem_delta[gs].alloc(cap);
+      a.amb[gs] = amb[gs].p; a.delta[gs] = chem_delta[gs].p; fin.delta[gs] = chem_delta[gs].p;
+    }
+    a.dt = T(T(dt) / sstp_chem); a.chem_rho = T(o.chem_rho); a.dsl = dsl; a.dsc = opts.chem_dsc != 0; a.rct = opts.chem_rct != 0;
+    for (int step = 0; step < sstp_chem; ++step) {
+      if (npart) hipLaunchKernelGGL(k_chem<T>, dim3(nblk(npart)), dim3(BS), 0, st, a);
+      if (dsl) {
+        fin.next_step = step + 1 < sstp_chem ? step + 1 : 0;
+        hipLaunchKernelGGL(k_chem_cellfinish<T>, dim3(nblk(ncell, BS / WAVE)), dim3(BS), 0, st, fin);
+      }
+    }
+  }
+  // bcnd.ipp:330-340: what the move took out through the bottom, from the multiplicities saved ahead of it
+  void chem_puddle_add(size_t n)
+  {
+    const unsigned blocks = nblk(n);
+    puddle_chem_partial.alloc(size_t(blocks) * CH_ALL);
+    hipLaunchKernelGGL(k_chem_puddle<T>, dim3(blocks), dim3(BS), 0, st, n, chem_n_before.p, A.n.p, A.x.p, A.y.p, A.z.p, T(o.x0), T(o.x1), T(o.y0), T(o.y1), T(o.z0),
+                       o.open_side_walls, chem_ptrs(), puddle_chem_partial.p);
+    hipLaunchKernelGGL(k_chem_puddle_sum, dim3(1), dim3(BS), 0, st, puddle_chem_partial.p, size_t(blocks), puddle_chem.p);
+  }
+  void diag_chem(int species) override
+  {                                                                                      // particles_diag.ipp:643-650
+    if (!o.chem_switch) throw lcx_error("libcloudph++: chemistry is switched off in opts_init, but diag_chem was called");
+    if (species < 0 || species >= CH_ALL) throw lcx_error("libcloudph++ (HIP): diag_chem: no such chemical species");
+    moms_sum(A.ext[ix_chem + species].p, T(1), 0, true);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -2269,11 +2376,13 @@ struct Particles : IParticles {
     courant_checks(cx, cy, cz);
     if (turb_any() && is_null(diss)) throw lcx_error("libcloudph++: turbulent advection, coalescence and condesation are not switched off and diss_rate is empty");
     if (!turb_any() && !is_null(diss)) throw lcx_error("libcloudph++: turbulent advection, coalescence and condesation are switched off and diss_rate is not empty");
+    chem_check_arg();
     Range r(this, "sync_in");
     var_rho = !is_null(rhod_);
     stage_begin();
     sync_in_arr(th_, th, ncell, 0, 0, 0); sync_in_arr(rv_, rv, ncell, 0, 0, 0); sync_in_arr(rhod_, rhod, ncell, 0, 0, 0);
     if (turb_any()) sync_in_arr(diss, diss_rate, ncell, 0, 0, 0);
+    if (o.chem_switch) chem_sync_in();
     if (!courants_late) { sync_in_arr(cx, courant_x, n_cx, 1, 0, 0, halo); sync_in_arr(cy, courant_y, n_cy, 0, 1, 0, halo); sync_in_arr(cz, courant_z, n_cz, 0, 0, 1, halo); }
     flush_sync_jobs(); flush_host_in();
     if (o.adve_scheme == LCX_ADVE_PRED_CORR && !is_null(cx) && n_cx) {                  // particles_step.ipp:127-142
@@ -2289,6 +2398,9 @@ struct Particles : IParticles {
   {
     if (!should_now_run_cond) throw lcx_error("libcloudph++: please call sync_in() before calling step_cond()");
     if (opts.turb_cond && !o.turb_cond_switch) throw lcx_error("libcloudph++: turb_cond_swtich=False, but turb_cond==True");
+    const bool chem_now = opts.chem_dsl || opts.chem_dsc || opts.chem_rct;
+    if (chem_now && !o.chem_switch) throw lcx_error("libcloudph++: all chemistry was switched off");      // chem_ante.ipp:70
+    chem_check_arg(opts.chem_dsl != 0);            // (the gases are written to the caller's arrays with chem_dsl only)
     should_now_run_cond = false;
     adjust_timesteps(opts.dt);
     if (ix_ict >= 0 && nphys)                                                            // update_incloud_time, particles_step.ipp:180-181
@@ -2308,7 +2420,14 @@ struct Particles : IParticles {
         cond_substep(opts.RH_max, step, opts.turb_cond);                                 // (hskpng_mfp at substep 0 and hskpng_Tpr inside)
       }
       sstp_save();
-      { Range r(this, "sync_out"); sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); flush_sync_jobs(); }
+      if (!chem_now) { Range r(this, "sync_out"); sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); flush_sync_jobs(); }
+    }
+    if (chem_now) {                                // (after condensation, ahead of the results going out: particles_step.ipp:269-327)
+      chem_step(opts);
+      Range r(this, "sync_out");
+      if (opts.cond) { sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); }
+      if (opts.chem_dsl) for (int gs = 0; gs < CH_GAS; ++gs) sync_out_arr(amb[gs], chem_arg[gs], ncell);
+      flush_sync_jobs();
     }
     late_courants();               // (host rows and copies while the kernels queued above run)
     // opts_init.stream_ordered: nothing of this call touches host memory -- the results are ordered on the stream, the host goes on
@@ -2322,7 +2441,7 @@ struct Particles : IParticles {
   {
     if (!should_now_run_async) throw lcx_error("libcloudph++: please call step_sync() before calling step_async() again");
     should_now_run_async = false;
-    if (opts.chem_dsl || opts.chem_dsc || opts.chem_rct) throw lcx_error("libcloudph++: all chemistry was switched off in opts_init");
+    if ((opts.chem_dsl || opts.chem_dsc || opts.chem_rct) && !o.chem_switch) throw lcx_error("libcloudph++: all chemistry was switched off in opts_init");
     if (opts.coal && !o.coal_switch) throw lcx_error("libcloudph++: coalescence was switched off in opts_init");
     if (opts.sedi && !o.sedi_switch) throw lcx_error("libcloudph++: sedimentation was switched off in opts_init");
     if (opts.subs && !o.subs_switch) throw lcx_error("libcloudph++: subsidence was switched off in opts_init");
@@ -2342,6 +2461,7 @@ struct Particles : IParticles {
     // Relaxation (never together with a source in one object): a step in which it does not fire launches what it launches without
     // opts.rlx.  A firing on a single device keeps the fused move like the simple source; short of room for the most it can create, or
     // with neighbours, it takes the plain sequence.
+    if (opts.chem_dsl && o.chem_switch) sstp_save_chem();                                // particles_step.ipp:367-372
     const bool rlx_now = opts.rlx && rlx_fires();
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
@@ -2372,7 +2492,10 @@ struct Particles : IParticles {
     const bool fused = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain;
     hold_big_list = fused && (src_now || rlx_now);
     if (rlx_now) rlx_census_and_plan();              // (on the cells of the step's start, before the move rewrites ijk)
+    const size_t n_chem_pud = o.chem_switch && n_dims > 1 && !o.periodic_topbot_walls ? nphys : 0;
+    if (n_chem_pud) { chem_n_before.alloc(cap); HIPCHK(hipMemcpyAsync(chem_n_before.p, A.n.p, n_chem_pud * sizeof(n_t), hipMemcpyDeviceToDevice, st)); }
     move(opts.adve, opts.sedi, opts.subs, true, fused);
+    if (n_chem_pud) chem_puddle_add(n_chem_pud);
     hold_big_list = false;
     adve_scheme = o.adve_scheme;
     // The reference appends the source's super-droplets before the boundary conditions (particles_step.ipp:448-479); here those are
@@ -2515,6 +2638,7 @@ struct Particles : IParticles {
     double s4[4];
     read_back(s4, puddle_acc.p, 4);
     puddle[LCX_OUT_LIQ_VOL] = s4[0]; puddle[LCX_OUT_DRY_VOL] = s4[1]; puddle[LCX_OUT_LIQ_NUM] = s4[2]; puddle[LCX_OUT_PRTCL_NUM] = s4[3];
+    if (o.chem_switch) { double s8[CH_ALL]; read_back(s8, puddle_chem.p, CH_ALL); for (int sp = 0; sp < CH_ALL; ++sp) puddle[LCX_OUT_HNO3 + sp] = s8[sp]; }
     for (int i = 0; i < LCX_OUT_COUNT; ++i) out[i] = puddle[i];
   }
   size_t n_part() override { return npart; }
@@ -2614,7 +2738,15 @@ struct Particles : IParticles {
       {"dot_ssp", ix_dot_ssp >= 0 ? A.ext[ix_dot_ssp].p : nullptr, ix_dot_ssp >= 0 ? npart : 0},
       {"diss_rate", diss_rate.p, turb_any() ? ncell : 0},
       {"raw_rlx_edges", rlx_edges.p, rlx_edges.p ? rlx_tab.edges.size() : 0}, {"raw_rlx_conc", rlx_conc.p, rlx_conc.p ? rlx_tab.conc.size() : 0}};
-    for (const E &e : tab)
+    static const char *const chem_names[CH_ALL] = {"HNO3", "NH3", "CO2", "SO2", "H2O2", "O3", "S_VI", "H"};
+    std::vector<E> all(std::begin(tab), std::end(tab));
+    std::string chem_nm[2 * CH_ALL];
+    if (o.chem_switch) {
+      for (int sp = 0; sp < CH_ALL; ++sp) { chem_nm[sp] = std::string("chem_") + chem_names[sp]; all.push_back(E{chem_nm[sp].c_str(), A.ext[ix_chem + sp].p, npart}); }
+      for (int gs = 0; gs < CH_GAS; ++gs) { chem_nm[CH_ALL + gs] = std::string("ambient_") + chem_names[gs]; all.push_back(E{chem_nm[CH_ALL + gs].c_str(), amb[gs].p, ncell}); }
+      all.push_back(E{"chem_flag", A.ext[ix_chem_flag].p, npart}); all.push_back(E{"chem_V", A.ext[ix_chem_V].p, npart});
+    }
+    for (const E &e : all)
       if (s == e.nm) {
         *n = e.len;
         if (!out) return;
@@ -2644,6 +2776,7 @@ struct Particles : IParticles {
     for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0 && n) HIPCHK(hipMemsetAsync(A.ext[ix].p, 0, n * sizeof(T), st));
     if (ix_tag >= 0 && n) hipLaunchKernelGGL(k_fill_index<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_tag].p, n);
     tag_next = n;
+    if (o.chem_switch) chem_init_masses(n);
     if (use_rc2 && n) { hipLaunchKernelGGL(k_fill<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_rc2].p, n, T(-1)); hskpng_approximate_rc2_invalid(); }
     sstp_save();
     hskpng_count();
@@ -3120,6 +3253,30 @@ int lcx_step_sync(lcx_particles *h, const lcx_opts_t *o, const lcx_arrinfo_t *th
                   const lcx_arrinfo_t *cx, const lcx_arrinfo_t *cy, const lcx_arrinfo_t *cz, const lcx_arrinfo_t *diss)
 { LCX_TRY(H->step_sync(*o, th, rv, rhod, cx, cy, cz, diss)) }
 int lcx_step_async(lcx_particles *h, const lcx_opts_t *o) { LCX_TRY(H->step_async(*o)) }
+// aqueous chemistry (include/lcx_chem.h): the existing entries with the six ambient arrays handed to the object for the call
+struct ChemArg {
+  IParticles *p;
+  ChemArg(IParticles *p_, const lcx_arrinfo_t *const *a) : p(p_)
+  {
+    bool given = false;
+    if (a) for (int g = 0; g < 6; ++g) if (a[g] && a[g]->data && a[g]->strides) given = true;
+    if (!p->chem_on() && given) throw std::runtime_error("libcloudph++: chemistry was switched off and ambient_chem is not empty");
+    p->chem_arg = a;
+  }
+  ~ChemArg() { p->chem_arg = nullptr; }
+};
+int lcx_init_chem(lcx_particles *h, const lcx_arrinfo_t *th, const lcx_arrinfo_t *rv, const lcx_arrinfo_t *rhod, const lcx_arrinfo_t *p,
+                  const lcx_arrinfo_t *cx, const lcx_arrinfo_t *cy, const lcx_arrinfo_t *cz, const lcx_arrinfo_t *ambient_chem[6])
+{ LCX_TRY({ IParticles *q = H; ChemArg g(q, ambient_chem); q->init(th, rv, rhod, p, cx, cy, cz); }) }
+int lcx_sync_in_chem(lcx_particles *h, const lcx_arrinfo_t *th, const lcx_arrinfo_t *rv, const lcx_arrinfo_t *rhod, const lcx_arrinfo_t *cx,
+                     const lcx_arrinfo_t *cy, const lcx_arrinfo_t *cz, const lcx_arrinfo_t *diss, const lcx_arrinfo_t *ambient_chem[6])
+{ LCX_TRY({ IParticles *q = H; ChemArg g(q, ambient_chem); q->sync_in(th, rv, rhod, cx, cy, cz, diss); }) }
+int lcx_step_cond_chem(lcx_particles *h, const lcx_opts_t *o, const lcx_arrinfo_t *th, const lcx_arrinfo_t *rv, const lcx_arrinfo_t *ambient_chem[6])
+{ LCX_TRY({ IParticles *q = H; ChemArg g(q, ambient_chem); q->step_cond(*o, th, rv); }) }
+int lcx_step_sync_chem(lcx_particles *h, const lcx_opts_t *o, const lcx_arrinfo_t *th, const lcx_arrinfo_t *rv, const lcx_arrinfo_t *rhod,
+                       const lcx_arrinfo_t *cx, const lcx_arrinfo_t *cy, const lcx_arrinfo_t *cz, const lcx_arrinfo_t *diss, const lcx_arrinfo_t *ambient_chem[6])
+{ LCX_TRY({ IParticles *q = H; ChemArg g(q, ambient_chem); q->step_sync(*o, th, rv, rhod, cx, cy, cz, diss); }) }
+int lcx_diag_chem(lcx_particles *h, int species) { LCX_TRY(H->diag_chem(species)) }
 int lcx_diag_sd_conc(lcx_particles *h) { LCX_TRY(H->diag_sd_conc()) }
 int lcx_diag_pressure(lcx_particles *h) { LCX_TRY(H->diag_cell(0)) }
 int lcx_diag_temperature(lcx_particles *h) { LCX_TRY(H->diag_cell(1)) }

@@ -2795,7 +2795,7 @@ __global__ void __launch_bounds__(BS) k_alive_tiles(const n_t *n, size_t n_part,
   if (threadIdx.x == 0) { uint32_t s = 0; for (int w = 0; w < BS / WAVE; ++w) s += lds[w]; tile_sums[blockIdx.x] = s; }
 }
 // ext[]: further real-valued attributes that travel with a super-droplet (per-particle substepping state, rc2)
-constexpr int MAX_EXT = 12;
+constexpr int MAX_EXT = 24;      // (12 of condensation, turbulence and the tests + chemistry's 8 masses, volume and flag)
 template <class T> struct attr_set { n_t *n; T *rd3, *rw2, *kpa, *vt, *x, *y, *z; T *ext[MAX_EXT]; int n_ext; };
 
 template <class T>
@@ -3710,6 +3710,339 @@ __global__ void k_math_probe(int which, double *v, size_t n)
   const double x = v[i];
   v[i] = which == 0 ? cbrt_seeded(x) : which == 1 ? exp_reduced(x) : which == 2 ? cbrt(x) : which == 4 ? rcp_refined(x) : which == 5 ? log_lean(x) :
          which == 6 ? rcp_newton1(x) : which == 7 ? cbrt1p<true>(x) : which == 8 ? exp_kelvin(x) : which == 9 ? exp_lib(x) : exp(x);
+}
+
+// ============================================================================================
+// aqueous chemistry (src/impl/chemistry/*.ipp; common/{henry,dissoc,react,molar_mass}.hpp): opts_init.chem_switch.
+// Eight masses per super-droplet (kg per real droplet, common::chem order) travel as extension attributes.  A substep is ONE launch
+// over the droplets in the cell-sorted order (k_chem: volume and dilute-droplet flag, Henry's law for the six gases, the H+ mass of
+// electroneutrality, the oxidation of S(IV) by RK4 and the dry radius, a droplet's masses in registers throughout) and one wave per
+// cell that sums what the cell's droplets took up of each gas and lowers the ambient mixing ratios (k_chem_cellfinish).  What depends
+// on the temperature alone is evaluated once per cell and step (k_chem_cellpre).
+// ============================================================================================
+enum { CH_HNO3 = 0, CH_NH3, CH_CO2, CH_SO2, CH_H2O2, CH_O3, CH_S_VI, CH_H, CH_ALL, CH_GAS = 6 };
+template <class T> struct chem_cst {
+  static constexpr T M_SO2 = T(64 * 1e-3), M_H2O2 = T(34 * 1e-3), M_O3 = T(48 * 1e-3), M_NH3 = T(17 * 1e-3), M_HNO3 = T(63 * 1e-3), M_CO2 = T(44 * 1e-3);
+  static constexpr T M_H = T(1 * 1e-3), M_SO2_H2O = T(82 * 1e-3), M_NH3_H2O = T(35 * 1e-3), M_NH4 = T(18 * 1e-3), M_CO2_H2O = T(62 * 1e-3);
+  static constexpr T M_H2SO4 = T(98 * 1e-3), M_HSO4 = T(97 * 1e-3);
+  static constexpr T K_H2O = T(1e-14 * 1e6), K_SO2 = T(1.3e-2 * 1e3), K_HSO3 = T(6.6e-8 * 1e3), K_HSO4 = T(1.2e-2 * 1e3), K_CO2 = T(4.3e-7 * 1e3);
+  static constexpr T K_HCO3 = T(4.68e-11 * 1e3), K_NH3 = T(1.7e-5 * 1e3), K_HNO3 = T(15.4 * 1e3);
+  static constexpr T dKR_CO2 = T(-1000.), dKR_HCO3 = T(-1760.), dKR_SO2 = T(1960.), dKR_HSO3 = T(1500.), dKR_NH3 = T(-450.), dKR_HNO3 = T(8700.), dKR_HSO4 = T(2720.);
+  static constexpr T R_S_H2O2_k = T(7.5 * 1e7 * 1e-6), R_S_H2O2_K = T(13. * 1e-3), R_S_O3_k0 = T(2.4 * 1e4 * 1e-3), R_S_O3_k1 = T(3.7 * 1e5 * 1e-3), R_S_O3_k2 = T(1.5 * 1e9 * 1e-3);
+  static constexpr T dER_H2O2_k = T(-4430.), dER_O3_k0 = T(0.), dER_O3_k1 = T(-5530.), dER_O3_k2 = T(-5280.);
+};
+// Henry constant at 298 K, its temperature coefficient, molar mass of the gas and of its dissolved form, gas-phase diffusivity, accommodation coefficient
+template <class T> struct chem_gas_par { T H, dHR, M_gas, M_aq, D, ac; };
+template <class T> LCX_HD chem_gas_par<T> chem_gas(int g)
+{
+  using c = chem_cst<T>;
+  const T p_stp = cst<T>::p_stp;
+  switch (g) {
+    case CH_HNO3: return {T(2.1 * 1e5 * 1e3) / p_stp, T(8700.), c::M_HNO3, c::M_HNO3, T(.6525 * 1e-4), T(.05)};
+    case CH_NH3:  return {T(62 * 1e3) / p_stp, T(4100.), c::M_NH3, c::M_NH3_H2O, T(.1978 * 1e-4), T(.05)};
+    case CH_CO2:  return {T(3.4 * 1e-2 * 1e3) / p_stp, T(2440.), c::M_CO2, c::M_CO2_H2O, T(.1381 * 1e-4), T(.05)};
+    case CH_SO2:  return {T(1.23 * 1e3) / p_stp, T(3150.), c::M_SO2, c::M_SO2_H2O, T(.1089 * 1e-4), T(.035)};
+    case CH_H2O2: return {T(7.45e4 * 1e3) / p_stp, T(7300.), c::M_H2O2, c::M_H2O2, T(.8700 * 1e-4), T(.018)};
+    default:      return {T(1.13 * 1e-2 * 1e3) / p_stp, T(2540.), c::M_O3, c::M_O3, T(.1444 * 1e-4), T(.00053)};
+  }
+}
+// what depends on the temperature alone: the seven dissociation constants, the four reaction rates, the six Henry constants and the
+// mean molecular speeds of the gases (dissoc.hpp K_temp, react.hpp R_temp_*, henry.hpp H_temp / molec_vel)
+template <class T> struct chem_cell { T K_SO2, K_HSO3, K_CO2, K_HCO3, K_NH3, K_HNO3, K_HSO4, R_O3_k0, R_O3_k1, R_O3_k2, R_H2O2_k, H[CH_GAS], mv[CH_GAS]; };
+template <class T> LCX_HD T chem_arrhenius(T Tk, T K, T dKR) { return K * exp(dKR * (T(1.) / Tk - T(1. / 298))); }
+template <class T> LCX_HD chem_cell<T> make_chem_cell(T Tk)
+{
+  using c = chem_cst<T>;
+  chem_cell<T> k;
+  k.K_SO2 = chem_arrhenius(Tk, c::K_SO2, c::dKR_SO2); k.K_HSO3 = chem_arrhenius(Tk, c::K_HSO3, c::dKR_HSO3);
+  k.K_CO2 = chem_arrhenius(Tk, c::K_CO2, c::dKR_CO2); k.K_HCO3 = chem_arrhenius(Tk, c::K_HCO3, c::dKR_HCO3);
+  k.K_NH3 = chem_arrhenius(Tk, c::K_NH3, c::dKR_NH3); k.K_HNO3 = chem_arrhenius(Tk, c::K_HNO3, c::dKR_HNO3);
+  k.K_HSO4 = chem_arrhenius(Tk, c::K_HSO4, c::dKR_HSO4);
+  k.R_O3_k0 = chem_arrhenius(Tk, c::R_S_O3_k0, c::dER_O3_k0); k.R_O3_k1 = chem_arrhenius(Tk, c::R_S_O3_k1, c::dER_O3_k1);
+  k.R_O3_k2 = chem_arrhenius(Tk, c::R_S_O3_k2, c::dER_O3_k2); k.R_H2O2_k = chem_arrhenius(Tk, c::R_S_H2O2_k, c::dER_H2O2_k);
+#pragma unroll
+  for (int g = 0; g < CH_GAS; ++g) {
+    const chem_gas_par<T> gp = chem_gas<T>(g);
+    k.H[g] = chem_arrhenius(Tk, gp.H, gp.dHR);
+    k.mv[g] = T(sqrt(T(8.) / cst<T>::pi * (cst<T>::kaBoNA * Tk / gp.M_gas)));
+  }
+  return k;
+}
+// sstp_chem.ipp:53-102: the ambient fields' share of a substep.  step 0: tmp := new - old, field := new - (sstp - 1) tmp / sstp;
+// later substeps: field += tmp / sstp
+template <class T> LCX_HD void chem_sstp_step(int step, T sstp, T &scl, T &tmp)
+{
+  if (step == 0) { tmp = scl - tmp; scl = scl - (sstp - 1) * tmp / sstp; }
+  else scl = scl + tmp / sstp;
+}
+template <class T> struct chem_fields { T *amb[CH_GAS], *tmp[CH_GAS]; };
+// once per step: the temperature factors of every cell and substep 0 of the ambient fields (n_sstp of them, 0: no substepping)
+// (ccd: a float object's factors in double as well, for the H+ root -- see k_chem)
+template <class T>
+__global__ void k_chem_cellpre(size_t n_cell, const T *Tk, chem_cell<T> *cc, chem_cell<double> *ccd, chem_fields<T> f, int n_sstp, T sstp)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  cc[c] = make_chem_cell<T>(Tk[c]);
+  if (ccd) ccd[c] = make_chem_cell<double>(double(Tk[c]));
+  for (int g = 0; g < n_sstp; ++g) { T scl = f.amb[g][c], tmp = f.tmp[g][c]; chem_sstp_step(0, sstp, scl, tmp); f.amb[g][c] = scl; f.tmp[g][c] = tmp; }
+}
+// ionic strength below 0.02 mol / l (chem_strength.ipp:14-67): the droplets dilute enough for the chemistry
+template <class T> LCX_HD bool chem_dilute(const T (&m)[CH_ALL], T V, const chem_cell<T> &k)
+{
+  using c = chem_cst<T>;
+  const T S_IV = m[CH_SO2] / c::M_SO2_H2O / V, C_IV = m[CH_CO2] / c::M_CO2_H2O / V, N_V = m[CH_HNO3] / c::M_HNO3 / V;
+  const T N_III = m[CH_NH3] / c::M_NH3_H2O / V, S_VI = m[CH_S_VI] / c::M_H2SO4 / V, H = m[CH_H] / c::M_H / V;
+  return T(0.5) * (H + c::K_H2O / H + H * S_VI / (H + k.K_HSO4) + T(4) * k.K_HSO4 * S_VI / (H + k.K_HSO4) +
+                   k.K_CO2 * H * C_IV / (H * H + k.K_CO2 * H + k.K_CO2 * k.K_HCO3) + T(4) * k.K_CO2 * k.K_HCO3 * C_IV / (H * H + k.K_CO2 * H + k.K_CO2 * k.K_HCO3) +
+                   k.K_SO2 * H * S_IV / (H * H + k.K_SO2 * H + k.K_SO2 * k.K_HSO3) + T(4) * k.K_SO2 * k.K_HSO3 * S_IV / (H * H + k.K_SO2 * H + k.K_SO2 * k.K_HSO3) +
+                   k.K_HNO3 * N_V / (H + k.K_HNO3) + k.K_NH3 * H * N_III / (c::K_H2O + k.K_NH3 * H)) < T(0.02 * 1000);
+}
+// Henry's law for gas g over the substep, implicit (chem_henry.ipp:64-240; Warneck, eq. 8.22)
+template <class T> LCX_HD T chem_henry_mass(int g, T m_old, T m_H, T V, T rw2, T Tk, T c_amb, T rhod, T dt, const chem_cell<T> &k)
+{
+  using c = chem_cst<T>;
+  const chem_gas_par<T> gp = chem_gas<T>(g);
+  const T conc_H = m_H / c::M_H / V;
+  T hlp = T(1);
+  if (g == CH_SO2) hlp = T(1) + k.K_SO2 / conc_H + k.K_SO2 * k.K_HSO3 / conc_H / conc_H;
+  else if (g == CH_CO2) hlp = T(1) + k.K_CO2 / conc_H + k.K_CO2 * k.K_HCO3 / conc_H / conc_H;
+  else if (g == CH_HNO3) hlp = T(1) + k.K_HNO3 / conc_H;
+  else if (g == CH_NH3) hlp = T(1.) + k.K_NH3 / c::K_H2O * conc_H;
+  const T henry = (g == CH_O3 || g == CH_H2O2) ? k.H[g] : k.H[g] * hlp;
+  const T mass_trans = T(1.) / (rw2 / T(3.) / gp.D + T(4. / 3.) / gp.ac * T(sqrt(rw2)) / k.mv[g]);
+  return (m_old + dt * V * mass_trans * c_amb * rhod * (gp.M_aq / gp.M_gas)) / (T(1.) + dt * mass_trans / henry / cst<T>::kaBoNA / Tk);
+}
+// chem_dissoc.ipp:17-99: H+ present minus H+ that electroneutrality asks for
+template <class T> struct chem_minfun {
+  T m_S_IV, m_C_IV, m_N_V, m_N_III, m_S_VI, V; chem_cell<T> k;
+  LCX_HD T operator()(T m_H) const
+  {
+    using c = chem_cst<T>;
+    const T conc_H = m_H / c::M_H / V;
+    return -m_H + c::M_H * (
+      c::K_H2O * c::M_H * (V * V) / m_H
+      + m_S_IV / c::M_SO2_H2O * k.K_SO2 / conc_H / (T(1) + k.K_SO2 / conc_H + k.K_SO2 * k.K_HSO3 / conc_H / conc_H)
+      + T(2) * m_S_IV / c::M_SO2_H2O * k.K_SO2 * k.K_HSO3 / conc_H / conc_H / (T(1) + k.K_SO2 / conc_H + k.K_SO2 * k.K_HSO3 / conc_H / conc_H)
+      + conc_H * m_S_VI / c::M_H2SO4 / (conc_H + k.K_HSO4)
+      + T(2) * k.K_HSO4 * m_S_VI / c::M_H2SO4 / (conc_H + k.K_HSO4)
+      + m_C_IV / c::M_CO2_H2O * k.K_CO2 / conc_H / (T(1) + k.K_CO2 / conc_H + k.K_CO2 * k.K_HCO3 / conc_H / conc_H)
+      + T(2) * m_C_IV / c::M_CO2_H2O * k.K_CO2 * k.K_HCO3 / conc_H / conc_H / (T(1) + k.K_CO2 / conc_H + k.K_CO2 * k.K_HCO3 / conc_H / conc_H)
+      + m_N_V / c::M_HNO3 * k.K_HNO3 / conc_H / (T(1.) + k.K_HNO3 / conc_H)
+      - m_N_III / c::M_NH3_H2O * k.K_NH3 / c::K_H2O * conc_H / (T(1) + k.K_NH3 / c::K_H2O * conc_H));
+  }
+};
+// chem_dissoc.ipp:101-140: TOMS748 between 1e-8 and 10 mol / l, to the tolerance the reference asks for (eps_tolerance<float>(32)
+// whatever real_t is, 98 iterations at most: its four-argument entry spends two on the ends of the bracket)
+template <class T> LCX_HD T chem_electroneutral_H(const T (&m)[CH_ALL], T V, const chem_cell<T> &k)
+{
+  const chem_minfun<T> f{m[CH_SO2], m[CH_CO2], m[CH_HNO3], m[CH_NH3], m[CH_S_VI], V, k};
+  const T rht = T(1e1 * 1e3) * V * chem_cst<T>::M_H, lft = T(1e-8 * 1e3) * V * chem_cst<T>::M_H;
+  return toms748_solve(f, lft, rht, f(lft), f(rht), T(4 * lim<float>::eps), 98u);
+}
+// chem_react.ipp:17-117: mass tendencies of (S_IV, H2O2, O3, S_VI) by the oxidation with O3 and H2O2; H+, T and V are frozen
+template <class T> LCX_HD void chem_react_rhs(T m_S_IV, T m_H2O2, T m_O3, T m_H, T V, T dt, const chem_cell<T> &k, T (&dot)[4])
+{
+  using c = chem_cst<T>;
+  const T conc_H = m_H / c::M_H / V;
+  const T diss = T(1) + k.K_SO2 / conc_H + k.K_SO2 * k.K_HSO3 / conc_H / conc_H;
+  T O3_react = V * m_O3 / c::M_O3 / V * m_S_IV / c::M_SO2_H2O / V / diss
+               * (k.R_O3_k0 + k.R_O3_k1 * k.K_SO2 / conc_H + k.R_O3_k2 * k.K_SO2 * k.K_HSO3 / conc_H / conc_H);
+  O3_react = (O3_react * dt < m_O3 / c::M_O3) ? O3_react : m_O3 / c::M_O3 / dt;
+  O3_react = (O3_react * dt < m_S_IV / c::M_SO2_H2O) ? O3_react : m_S_IV / c::M_SO2_H2O / dt;
+  T H2O2_react = V * k.R_H2O2_k * k.K_SO2 * m_H2O2 / c::M_H2O2 / V * m_S_IV / c::M_SO2_H2O / V / diss / (T(1) + c::R_S_H2O2_K * conc_H);
+  H2O2_react = (H2O2_react * dt < m_H2O2 / c::M_H2O2) ? H2O2_react : m_H2O2 / c::M_H2O2 / dt;
+  H2O2_react = (H2O2_react * dt < m_S_IV / c::M_SO2_H2O - O3_react * dt) ? H2O2_react : m_S_IV / c::M_SO2_H2O / dt - O3_react;
+  dot[0] = -(c::M_SO2_H2O * (O3_react + H2O2_react));
+  dot[1] = -(c::M_H2O2 * H2O2_react);
+  dot[2] = -(c::M_O3 * O3_react);
+  dot[3] = c::M_H2SO4 * (O3_react + H2O2_react);
+}
+template <class T> struct chem_args {
+  size_t n_part; const uint32_t *sorted_id, *sorted_ijk; const n_t *n; const T *rw2; T *rd3; T *m[CH_ALL]; T *V_out, *flag_out;
+  const chem_cell<T> *cc; const chem_cell<double> *ccd; const T *Tk, *rhod; const T *amb[CH_GAS]; T *delta[CH_GAS]; T dt, chem_rho; int dsl, dsc, rct;
+};
+// one chemistry substep of every droplet (particles_step.ipp:269-312), lane p <-> position p of the cell-sorted order.  delta[g][p] =
+// n (m_new - m_old) of gas g, what k_chem_cellfinish sums per cell
+template <class T>
+__global__ void __launch_bounds__(BS) k_chem(chem_args<T> a)
+{
+  const size_t p = gid(); if (p >= a.n_part) return;
+  const uint32_t id = a.sorted_id[p], cell = a.sorted_ijk[p];
+  const chem_cell<T> k = a.cc[cell];
+  const T Tk = a.Tk[cell], rw2 = a.rw2[id];
+  T m[CH_ALL];
+#pragma unroll
+  for (int s = 0; s < CH_ALL; ++s) m[s] = a.m[s][id];
+  const T V = T(4. / 3) * cst<T>::pi * T(pow(rw2, T(3. / 2)));          // chem_ante.ipp:15-32
+  const bool flag = chem_dilute(m, V, k);
+  a.V_out[id] = V; a.flag_out[id] = flag ? T(1) : T(0);
+  auto cleanup = [&]() {                                                  // chem_ante.ipp:34-57
+#pragma unroll
+    for (int s = 0; s < CH_ALL; ++s) m[s] = m[s] >= T(0.) ? m[s] : T(0.);
+  };
+  if (a.dsl) {
+    const T rhod = a.rhod[cell], nn = T(a.n[id]);
+#pragma unroll
+    for (int g = 0; g < CH_GAS; ++g) {
+      T d = T(0);
+      if (flag) {
+        const T m_new = chem_henry_mass<T>(g, m[g], m[CH_H], V, rw2, Tk, a.amb[g][cell], rhod, a.dt, k);
+        d = nn * (m_new - m[g]);
+        m[g] = m_new;
+      }
+      a.delta[g][p] = d;
+    }
+    cleanup();
+  }
+  if (a.dsc) {
+    if (flag) {
+      if constexpr (sizeof(T) == sizeof(double)) m[CH_H] = chem_electroneutral_H(m, V, k);
+      else {
+        // a float object: the electroneutrality function is a difference of nearly equal terms, and evaluated in float its root is only
+        // good to 1e-4 -- far from the tolerance the search is asked for.  The function (volume and dissociation constants included) is
+        // evaluated in double on the droplet's float state, the root rounded to float
+        double md[CH_ALL];
+#pragma unroll
+        for (int s = 0; s < CH_ALL; ++s) md[s] = double(m[s]);
+        const double Vd = 4. / 3 * cst<double>::pi * pow(double(rw2), 3. / 2);
+        m[CH_H] = T(chem_electroneutral_H(md, Vd, a.ccd[cell]));
+      }
+    }
+    cleanup();
+  }
+  if (a.rct) {
+    if (flag) {
+      // classical Runge-Kutta over (S_IV, H2O2, O3, S_VI), the stages in the order of the reference's stepper (chem_react.ipp:258-290)
+      const T x0[4] = {m[CH_SO2], m[CH_H2O2], m[CH_O3], m[CH_S_VI]}, dt = a.dt, mH = m[CH_H];
+      T k1[4], k2[4], k3[4], k4[4], x[4];
+      chem_react_rhs(x0[0], x0[1], x0[2], mH, V, dt, k, k1);
+      for (int i = 0; i < 4; ++i) x[i] = x0[i] + dt * T(.5) * k1[i];
+      chem_react_rhs(x[0], x[1], x[2], mH, V, dt, k, k2);
+      for (int i = 0; i < 4; ++i) x[i] = x0[i] + dt * T(.5) * k2[i];
+      chem_react_rhs(x[0], x[1], x[2], mH, V, dt, k, k3);
+      for (int i = 0; i < 4; ++i) x[i] = x0[i] + dt * k3[i];
+      chem_react_rhs(x[0], x[1], x[2], mH, V, dt, k, k4);
+      for (int i = 0; i < 4; ++i) x[i] = x0[i] + dt / T(6) * k1[i] + dt / T(3) * k2[i] + dt / T(3) * k3[i] + dt / T(6) * k4[i];
+      m[CH_SO2] = x[0]; m[CH_H2O2] = x[1]; m[CH_O3] = x[2]; m[CH_S_VI] = x[3];
+      a.rd3[id] = a.rd3[id] + (T(3. / 4) / cst<T>::pi / a.chem_rho) * (x[3] - x0[3]);      // chem_react.ipp:221-255
+    }
+    cleanup();
+  }
+#pragma unroll
+  for (int s = 0; s < CH_ALL; ++s) a.m[s][id] = m[s];
+}
+// One wave per cell: the ordered sum of the cell's delta[g] (each lane its positions in ascending order, then a fixed shuffle tree: the
+// same bits whenever the cell holds the same droplets in the same order), the new mixing ratio (chem_henry.ipp:28-62, clamped at 0; a
+// cell without droplets keeps its value) and, next_step > 0, the ambient fields' share of the NEXT substep
+template <class T> struct chem_fin_args {
+  size_t n_cell; const uint32_t *cell_start; const T *delta[CH_GAS]; chem_fields<T> f; const T *dv, *rhod; int henry, next_step, n_sstp; T sstp;
+};
+template <class T>
+__global__ void __launch_bounds__(BS) k_chem_cellfinish(chem_fin_args<T> a)
+{
+  const size_t c = size_t(blockIdx.x) * (BS / WAVE) + wave_id();
+  if (c >= a.n_cell) return;
+  const uint32_t s = a.cell_start[c], e = a.cell_start[c + 1];
+  const unsigned l = lane_id();
+#pragma unroll
+  for (int g = 0; g < CH_GAS; ++g) {
+    T scl = T(0);
+    if (l == 0) scl = a.f.amb[g][c];
+    if (a.henry && e > s) {
+      T acc = T(0);
+      for (uint32_t q = s + l; q < e; q += WAVE) acc += a.delta[g][q];
+#pragma unroll
+      for (int d = WAVE / 2; d > 0; d >>= 1) acc += __shfl_down(acc, d);
+      if (l == 0) {
+        const chem_gas_par<T> gp = chem_gas<T>(g);
+        const T new_c = scl - acc / gp.M_aq * gp.M_gas / a.dv[c] / a.rhod[c];
+        scl = new_c > 0 ? new_c : new_c * T(0);
+      }
+    }
+    if (l == 0) {
+      if (a.next_step > 0 && g < a.n_sstp) { T tmp = a.f.tmp[g][c]; chem_sstp_step(a.next_step, a.sstp, scl, tmp); }
+      a.f.amb[g][c] = scl;
+    }
+  }
+}
+// initial masses from the dry radius: the aerosol is NH4HSO4 of density chem_rho (init_chem.ipp:34-223)
+template <class T> struct chem_mass_ptrs { T *m[CH_ALL]; };
+template <class T>
+__global__ void k_chem_init(size_t n, const T *rd3, T chem_rho, chem_mass_ptrs<T> cm)
+{
+  const size_t i = gid(); if (i >= n) return;
+  using c = chem_cst<T>;
+  const T r = rd3[i];
+#pragma unroll
+  for (int s = 0; s < CH_ALL; ++s) cm.m[s][i] = T(0);
+  cm.m[CH_NH3][i] = T(4. / 3) * cst<T>::pi * chem_rho * r * (c::M_NH3_H2O / (c::M_NH4 + c::M_HSO4));
+  cm.m[CH_S_VI][i] = T(4. / 3) * cst<T>::pi * chem_rho * r * (c::M_H2SO4 / (c::M_NH4 + c::M_HSO4));
+  cm.m[CH_H][i] = T(4. / 3) * cst<T>::pi * chem_rho * r * (c::M_H / (c::M_NH4 + c::M_HSO4));
+}
+// coal.ipp:46-57,458-480 (summator): after a collision the super-droplet that keeps its multiplicity gains col x the other's masses.
+// col[p] > 0: collisions of the pair at positions (p, p + 1); col[p + 1] == -2: the first one had the greater OR EQUAL multiplicity
+template <class T>
+__global__ void k_coal_chem(size_t n_part, const uint32_t *sorted_id, const T *col, chem_mass_ptrs<T> cm)
+{
+  const size_t p = gid(); if (p + 1 >= n_part) return;
+  const T cn = col[p];
+  if (cn <= 0) return;
+  const uint32_t a = sorted_id[p], b = sorted_id[p + 1];
+  const bool na_ge_nb = col[p + 1] == T(-2);
+#pragma unroll
+  for (int s = 0; s < CH_ALL; ++s) {
+    if (na_ge_nb) cm.m[s][b] += cn * cm.m[s][a];
+    else cm.m[s][a] += cn * cm.m[s][b];
+  }
+}
+// bcnd.ipp:330-340: sum of n m over the super-droplets that the move has just taken out through the bottom (n_before: their multiplicities
+// ahead of the move; one that a side wall had removed first counts as nothing, bcnd.ipp:219-232), one partial of eight per workgroup
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_chem_puddle(size_t n, const n_t *n_before, const n_t *n_now, const T *x, const T *y, const T *z, T x0, T x1, T y0, T y1, T z0, int open_side_walls,
+              chem_mass_ptrs<T> cm, double *partial)
+{
+  __shared__ double red[CH_ALL][BS / WAVE];
+  const size_t i = gid();
+  bool out = false;
+  if (i < n && n_before[i] != 0 && n_now[i] == 0 && z[i] < z0) {
+    out = true;
+    if (open_side_walls && (x[i] >= x1 || x[i] < x0)) out = false;
+    if (open_side_walls && y && (y[i] >= y1 || y[i] < y0)) out = false;
+  }
+  double v[CH_ALL];
+#pragma unroll
+  for (int s = 0; s < CH_ALL; ++s) v[s] = out ? double(T(n_before[i])) * double(cm.m[s][i]) : 0.;
+  if (__ballot(out) != 0ull) {
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1)
+#pragma unroll
+      for (int s = 0; s < CH_ALL; ++s) v[s] += __shfl_down(v[s], d);
+  }
+  if (lane_id() == 0)
+#pragma unroll
+    for (int s = 0; s < CH_ALL; ++s) red[s][wave_id()] = v[s];
+  __syncthreads();
+  if (threadIdx.x < CH_ALL) {
+    double t = 0;
+    for (int w = 0; w < BS / WAVE; ++w) t += red[threadIdx.x][w];
+    partial[size_t(blockIdx.x) * CH_ALL + threadIdx.x] = t;
+  }
+}
+// the partials in their order by one workgroup (a lane its workgroups ascending, then a fixed tree), added to the running totals
+__global__ void __launch_bounds__(BS) k_chem_puddle_sum(const double *partial, size_t nblocks, double *running)
+{
+  __shared__ double red[CH_ALL][BS];
+  double acc[CH_ALL];
+  for (int s = 0; s < CH_ALL; ++s) acc[s] = 0;
+  for (size_t b = threadIdx.x; b < nblocks; b += BS) for (int s = 0; s < CH_ALL; ++s) acc[s] += partial[b * CH_ALL + s];
+  for (int s = 0; s < CH_ALL; ++s) red[s][threadIdx.x] = acc[s];
+  __syncthreads();
+  for (int d = BS / 2; d > 0; d >>= 1) {
+    if (int(threadIdx.x) < d) for (int s = 0; s < CH_ALL; ++s) red[s][threadIdx.x] += red[s][threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x < CH_ALL) running[threadIdx.x] = running[threadIdx.x] + red[threadIdx.x][0];
 }
 
 } // namespace lcx

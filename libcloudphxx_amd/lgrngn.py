@@ -76,15 +76,18 @@ class RH_formula_t(_bp_enum):       # lgrngn/RH_formula.hpp:8
     rv_tet = 3
 
 
-class chem_species_t(_bp_enum):        # common/chem.hpp via bindings/python/lib.cpp:257-265 (the chemistry itself is outside this library)
-    H = 0
-    SO2 = 1
-    O3 = 2
-    H2O2 = 3
-    CO2 = 4
-    NH3 = 5
-    HNO3 = 6
-    S_VI = 7
+class chem_species_t(_bp_enum):        # common/chem.hpp:8-22 (= enum lcx_chem_species, include/lcx_chem.h): the VALUES are the header's,
+    HNO3 = 0                           # whatever order bindings/python/lib.cpp:257-265 lists the names in
+    NH3 = 1
+    CO2 = 2
+    SO2 = 3
+    H2O2 = 4
+    O3 = 5
+    S_VI = 6
+    H = 7
+
+
+chem_gas_n = 6                         # the first six species are the trace gases (ambient_chem) and their dissolved forms
 
 
 class dbg(enum.IntFlag):
@@ -203,6 +206,7 @@ class _opts_init_c(C.Structure):
         ("src_x1", C.c_double), ("src_y1", C.c_double), ("src_z1", C.c_double),
         ("rlx_bins", C.c_int), ("supstp_rlx", C.c_int), ("rlx_sd_per_bin", C.c_double), ("rlx_timescale", C.c_double),
         ("rlx_dry_distros", C.POINTER(_rlx_distro_c)), ("n_rlx_dry_distros", C.c_int),
+        ("chem_rho", C.c_double),
     ]
 
 
@@ -328,8 +332,7 @@ class opts_init_t:
         # aerosol relaxation (rlx_switch, opts.rlx): {kappa: [spectrum at STP, [kappa_min, kappa_max], [z_min, z_max]]}
         self.rlx_dry_distros = {}
         self.rlx_bins, self.rlx_timescale, self.rlx_sd_per_bin, self.supstp_rlx = 0, 1., 0., 1
-        # fields of the parts that are outside this library (chemistry): kept so that scripts written
-        # for the reference can set and print them; the matching switches make the constructor throw
+        # aqueous chemistry (chem_switch, sstp_chem): density of the dry aerosol, > 0 with chem_switch
         self.chem_rho = 0.
         # extensions (include/lcx.h)
         self.n_x_tot = 0
@@ -425,7 +428,7 @@ class opts_t:
         self.RH_max = 44.
         self.dt = -1.
         self.chem = False    # accepted for source compatibility with the reference's tests (no-op)
-        self.chem_gas = {}   # ambient trace gases: a holder only (chemistry is outside this library)
+        self.chem_gas = {}   # a holder only, as in the reference's binding (the gases are passed as ambient_chem= to init / step_sync)
         # aerosol source (opts_init.src_type): {(kappa, rd_insol): (spectrum per second, sd_conc, supstp)} and
         # {(kappa, rd_insol): {radius: [concentration per second, sd_count, supstp]}}
         self.src_dry_distros = {}
@@ -577,28 +580,55 @@ class particles_t:
     def _p(ai):
         return C.byref(ai) if ai is not None else None
 
+    def _chem(self, ambient_chem):
+        """ambient_chem = {chem_species_t: array} -> const lcx_arrinfo_t *[6] indexed by species (include/lcx_chem.h); a species that the
+        dict lacks is a null entry, which the library answers as the reference answers a map of the wrong size"""
+        tab = (C.POINTER(_arrinfo_c) * chem_gas_n)()
+        for k, a in ambient_chem.items():
+            if not 0 <= int(k) < chem_gas_n:
+                raise RuntimeError("libcloudph++: ambient_chem holds the trace gases only (HNO3, NH3, CO2, SO2, H2O2, O3)")
+            ai = self._arr(a)
+            self._arr_keep.append(ai)
+            tab[int(k)] = C.pointer(ai)
+        return tab
+
     # -- API (particles.hpp:17-134)
-    def init(self, th, rv, rhod, p=None, Cx=None, Cy=None, Cz=None):
+    def init(self, th, rv, rhod, p=None, Cx=None, Cy=None, Cz=None, ambient_chem=None):
         self._arr_keep = []
         a = [self._arr(x) for x in (th, rv, rhod, p, Cx, Cy, Cz)]
-        self._chk(self._f("init")(self._h, *[self._p(x) for x in a]))
+        if ambient_chem:
+            self._chk(self._f("init_chem")(self._h, *[self._p(x) for x in a], self._chem(ambient_chem)))
+        else:
+            self._chk(self._f("init")(self._h, *[self._p(x) for x in a]))
 
-    def sync_in(self, th, rv, rhod=None, Cx=None, Cy=None, Cz=None, diss_rate=None):
+    def sync_in(self, th, rv, rhod=None, Cx=None, Cy=None, Cz=None, diss_rate=None, ambient_chem=None):
         self._arr_keep = []
         a = [self._arr(x) for x in (th, rv, rhod, Cx, Cy, Cz, diss_rate)]
-        self._chk(self._f("sync_in")(self._h, *[self._p(x) for x in a]))
+        if ambient_chem:
+            self._chk(self._f("sync_in_chem")(self._h, *[self._p(x) for x in a], self._chem(ambient_chem)))
+        else:
+            self._chk(self._f("sync_in")(self._h, *[self._p(x) for x in a]))
 
-    def step_cond(self, opts, th, rv):
+    def step_cond(self, opts, th, rv, ambient_chem=None):
         self._arr_keep = []
         a = [self._arr(x) for x in (th, rv)]
         oc = opts._to_c()
-        self._chk(self._f("step_cond")(self._h, C.byref(oc), *[self._p(x) for x in a]))
+        if ambient_chem:
+            self._chk(self._f("step_cond_chem")(self._h, C.byref(oc), *[self._p(x) for x in a], self._chem(ambient_chem)))
+        else:
+            self._chk(self._f("step_cond")(self._h, C.byref(oc), *[self._p(x) for x in a]))
 
-    def step_sync(self, opts, th, rv, rhod=None, Cx=None, Cy=None, Cz=None, diss_rate=None):
+    def step_sync(self, opts, th, rv, rhod=None, Cx=None, Cy=None, Cz=None, diss_rate=None, ambient_chem=None):
         self._arr_keep = []
         a = [self._arr(x) for x in (th, rv, rhod, Cx, Cy, Cz, diss_rate)]
         oc = opts._to_c()
-        self._chk(self._f("step_sync")(self._h, C.byref(oc), *[self._p(x) for x in a]))
+        if ambient_chem:
+            self._chk(self._f("step_sync_chem")(self._h, C.byref(oc), *[self._p(x) for x in a], self._chem(ambient_chem)))
+        else:
+            self._chk(self._f("step_sync")(self._h, C.byref(oc), *[self._p(x) for x in a]))
+
+    def diag_chem(self, species):
+        self._chk(self._f("diag_chem")(self._h, C.c_int(int(species))))
 
     def step_async(self, opts):
         oc = opts._to_c()

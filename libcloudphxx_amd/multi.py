@@ -53,6 +53,8 @@ def distmem_opts(opts_init, rank, size, self_ring=False):
     if opts_init.rlx_switch:
         raise RuntimeError("libcloudph++: aerosol relaxation: use the multi-device object (factory(backend_t.multi_HIP, ...)); "
                            "the one-process-per-GPU path does not carry it")
+    if opts_init.chem_switch:                      # init_sanity_check.ipp:131-132
+        raise RuntimeError("libcloudph++: chemistry is not compatible with MPI")
     oi = copy.copy(opts_init)
     oi.dry_distros = dict(opts_init.dry_distros)
     n_x_bfr = rank * get_dev_nx(opts_init.nx, 0, size)
