@@ -150,9 +150,11 @@ def clean(m):
     return [np.where(x >= 0, x, x * 0) for x in m]
 
 
-def substep(st, dt, dsl, dsc, rct, f, amb=None, info=None):
+def substep(st, dt, dsl, dsc, rct, f, amb=None, info=None, H_after_dsc=None):
     """one chemistry substep of the state `st` (masses, rw2, rd3 ... as read from the library) in precision f; amb: the cells' ambient
-    mixing ratios to use (default: the state's).  Returns (masses, rd3, ambient, V, flag); dsc takes the H+ root by bisection."""
+    mixing ratios to use (default: the state's).  Returns (masses, rd3, ambient, V, flag); dsc takes the H+ root by bisection, or, with
+    H_after_dsc, the given H+ masses (the library's own root, which a caller has held to the bisection's, so that what follows the
+    dissociation can be held to the closed-form bars)."""
     ijk = st["ijk"]
     T, rhod, dv = st["T"].astype(f)[ijk], st["rhod"].astype(f)[ijk], st["dv"].astype(f)
     k = cell_factors(st["T"].astype(f), f)
@@ -183,7 +185,10 @@ def substep(st, dt, dsl, dsc, rct, f, amb=None, info=None):
         k64 = cell_factors(st["T"], np.float64)
         k64 = {n: ([a[ijk] for a in v] if isinstance(v, list) else v[ijk]) for n, v in k64.items()}
         m64 = [x.astype(np.float64) for x in m]
-        m[H] = np.where(flag, root_by_bisection(m64, V.astype(np.float64), k64), m64[H]).astype(f)
+        if H_after_dsc is None:
+            m[H] = np.where(flag, root_by_bisection(m64, V.astype(np.float64), k64), m64[H]).astype(f)
+        else:
+            m[H] = np.where(flag, np.asarray(H_after_dsc, dtype=np.float64), m64[H]).astype(f)
         m = clean(m)
     if rct:
         lim = np.zeros(rw2.shape, dtype=bool)
@@ -208,10 +213,25 @@ def rv_at(RH, th, rhod):
     return rv
 
 
-class Box:
-    """a chemistry object, its fields and ambient arrays; stepped with condensation at slight supersaturation first"""
+# the arithmetic of an object: the parity mode that the suite pins, the API default (fast arithmetic, the reference's iterates) and the
+# mode that bench.py runs; (strict_fp, cond_solver) as h.assert_mode reads them back
+MODES = {"strict": (True, 0), "toms": (False, 1), "fast": (False, 0)}
 
-    def __init__(self, dims, sd_conc, real_t=np.float64, gases=ICICLE_GAS, cond_steps=6, empty_cell=None, **kw):
+
+def set_mode(oi, mode):
+    if mode == "toms":
+        h.api_default_opts(oi)
+        assert (bool(oi.strict_fp), int(oi.cond_solver)) == MODES["toms"]
+    else:
+        oi.strict_fp, oi.cond_solver = MODES[mode]
+    return oi
+
+
+class Box:
+    """a chemistry object, its fields and ambient arrays; stepped with condensation at slight supersaturation first.  mode: a key of
+    MODES; courant: the non-zero Courant numbers of h.box_fields instead of air at rest"""
+
+    def __init__(self, dims, sd_conc, real_t=np.float64, gases=ICICLE_GAS, cond_steps=6, empty_cell=None, mode="strict", courant=False, **kw):
         nx, nz = dims
         oi = lgrngn.opts_init_t()
         oi.nx, oi.nz = nx, nz
@@ -231,7 +251,8 @@ class Box:
         for k_, v in kw.items():
             assert hasattr(oi, k_), k_
             setattr(oi, k_, v)
-        self.oi, self.f = oi, np.dtype(real_t).type
+        set_mode(oi, mode)
+        self.oi, self.f, self.mode = oi, np.dtype(real_t).type, mode
         shp = tuple(n for n in (nx, nz) if n > 0) or (1,)
         rng = np.random.default_rng(5)
         self.rhod = (1.1 - 0.01 * rng.random(shp)).astype(real_t)
@@ -241,6 +262,8 @@ class Box:
         self.C = {}
         if nx and nz:
             self.C = dict(Cx=np.zeros((nx + 1, nz), dtype=real_t), Cz=np.zeros((nx, nz + 1), dtype=real_t))
+            if courant:
+                self.C = {k_: v.astype(real_t) for k_, v in h.box_fields(oi)[3].items()}
         self.p = h.hip_particles(oi, real_t)
         self.p.init(self.th, self.rv, self.rhod, ambient_chem=self.amb(), **self.C)
         if empty_cell is not None:
