@@ -202,7 +202,7 @@ int orc_create(const lcx_opts_init_t *oi, int real_kind, orc_particles **out)
   if (real_kind != (int)sizeof(real)) FAIL("oracle: this flavour computes in a real_t of %d bytes (liblcx_oracle.so: double, liblcx_oracle_f32.so: float)", (int)sizeof(real));
   if (oi->chem_switch || oi->ice_switch || oi->rlx_switch || oi->src_type)
     FAIL("libcloudph++: option outside the accelerated hot path (chem/ice/src/rlx)");
-  if (sizeof(real) == 4 && oi->sstp_cond_act > 1) FAIL("oracle (float flavour): sstp_cond_act > 1 needs the critical radius in double (orc_physics.h)");
+  if (sizeof(real) == 4 && oi->sstp_cond_act > 1) FAIL("oracle (float flavour): sstp_cond_act > 1 has not been checked against anything in float");
   orc_particles *s = NEW(orc_particles, 1);
   s->o = *oi;
   s->distros = NEW(lcx_distro_t, oi->n_dry_distros);

@@ -129,18 +129,32 @@ static inline real mm_rdrdt(real D, real K, real rho_v, real T, real RH, real aw
          (1. / D / rho_v + lv / K / RH / T * (lv / R_v / T - 1.));
 }
 
-/* ---- TOMS 748 (Alefeld, Potra, Shi 1995), the variant vendored by the reference:
- *      include/libcloudph++/common/detail/toms748.hpp:60-454 ---- */
-typedef real (*orc_fn)(real x, void *ctx);
-
-static inline int orc_tol_reached(real eps, real a, real b)
-{                                                   /* toms748.hpp:267-282 */
-  return fabs(a - b) <= eps * dmin(fabs(a), fabs(b));
-}
-static inline real orc_eps_tolerance(unsigned bits)
-{
-  return dmax((real)ldexpf(1.0f, 1 - (int)bits), 4 * ORC_EPS);
-}
+/* ---- TOMS 748 in `real` (orc_toms748.h): the equilibrium radius and condensation iterate in real_t ---- */
+#define T7R real
+#define T7(name) name
+#define T7_EPS ORC_EPS
+#define T7_MAX ORC_MAX
+#define T7_MIN ORC_MIN
+#include "orc_toms748.h"
+#undef T7R
+#undef T7
+#undef T7_EPS
+#undef T7_MAX
+#undef T7_MIN
+/* ---- and in double whatever real is: the critical radius (kappa_koehler.hpp:154-166) ---- */
+static inline dbl dmin_d(dbl a, dbl b) { return b < a ? b : a; }
+static inline dbl dmax_d(dbl a, dbl b) { return a < b ? b : a; }
+#define T7R dbl
+#define T7(name) name##_d
+#define T7_EPS DBL_EPSILON
+#define T7_MAX DBL_MAX
+#define T7_MIN DBL_MIN
+#include "orc_toms748.h"
+#undef T7R
+#undef T7
+#undef T7_EPS
+#undef T7_MAX
+#undef T7_MIN
 /* The root finders' tolerance follows sizeof(real_t) in the reference (eps_tolerance<real_t>(sizeof(real_t) * 8 / 4), config.hpp:39,
  * toms748.hpp:445-471): 2^-15 for real, 2^-7 for float.  This oracle computes in real; orc_set_real_bytes(4) makes it iterate to
  * FLOAT's tolerance, so that a float build of the product is compared with the iterates its own arithmetic is meant to take
@@ -148,113 +162,6 @@ static inline real orc_eps_tolerance(unsigned bits)
  * tolerance from it when it is created, rw3_eq reads it at every call -- a test sets it for the length of its run and resets it to 8. */
 static unsigned orc_real_bytes_v = sizeof(real);
 static inline real orc_real_eps(void) { return orc_eps_tolerance(orc_real_bytes_v * 8 / 4); }
-static inline real t748_safe_div(real num, real denom, real r)
-{                                                   /* toms748.hpp:124-138 */
-  if (fabs(denom) < 1 && fabs(denom * ORC_MAX) <= fabs(num)) return r;
-  return num / denom;
-}
-static inline real t748_secant(real a, real b, real fa, real fb)
-{                                                   /* toms748.hpp:140-160 */
-  const real tol = ORC_EPS * 5;
-  const real c = a - (fa / (fb - fa)) * (b - a);
-  if (c <= a + fabs(a) * tol || c >= b - fabs(b) * tol) return (a + b) / 2;
-  return c;
-}
-static inline real t748_quadratic(real a, real b, real d, real fa, real fb, real fd, unsigned count)
-{                                                   /* toms748.hpp:162-222 */
-  real B = t748_safe_div(fb - fa, b - a, ORC_MAX);
-  real A = t748_safe_div(fd - fb, d - b, ORC_MAX);
-  A = t748_safe_div(A - B, d - a, 0.);
-  if (A == 0) return t748_secant(a, b, fa, fb);
-  real c = copysign(1., A * fa) > 0 ? a : b;
-  for (unsigned i = 1; i <= count; ++i)
-    c -= t748_safe_div(fa + (B + A * (c - b)) * (c - a), B + A * (2 * c - a - b), 1 + c - a);
-  if (c <= a || c >= b) c = t748_secant(a, b, fa, fb);
-  return c;
-}
-static inline real t748_cubic(real a, real b, real d, real e, real fa, real fb, real fd, real fe)
-{                                                   /* toms748.hpp:224-262 */
-  const real q11 = (d - e) * fd / (fe - fd);
-  const real q21 = (b - d) * fb / (fd - fb);
-  const real q31 = (a - b) * fa / (fb - fa);
-  const real d21 = (b - d) * fd / (fd - fb);
-  const real d31 = (a - b) * fb / (fb - fa);
-  const real q22 = (d21 - q11) * fb / (fe - fb);
-  const real q32 = (d31 - q21) * fa / (fd - fa);
-  const real d32 = (d31 - q21) * fd / (fd - fa);
-  const real q33 = (d32 - q22) * fa / (fe - fa);
-  real c = q31 + q32 + q33 + a;
-  if (c <= a || c >= b) c = t748_quadratic(a, b, d, fa, fb, fd, 3);
-  return c;
-}
-typedef struct { real a, b, fa, fb, d, fd; } t748_state;
-static inline void t748_bracket(orc_fn f, void *ctx, t748_state *s, real c)
-{                                                   /* toms748.hpp:60-122 */
-  const real tol = ORC_EPS * 2;
-  if ((s->b - s->a) < 2 * tol * s->a) c = s->a + (s->b - s->a) / 2;
-  else if (c <= s->a + fabs(s->a) * tol) c = s->a + fabs(s->a) * tol;
-  else if (c >= s->b - fabs(s->b) * tol) c = s->b - fabs(s->a) * tol;
-  const real fc = f(c, ctx);
-  if (fc == 0) { s->a = c; s->fa = 0; s->d = 0; s->fd = 0; return; }
-  if (copysign(1., s->fa * fc) < 0) { s->d = s->b; s->fd = s->fb; s->b = c; s->fb = fc; }
-  else                              { s->d = s->a; s->fd = s->fa; s->a = c; s->fa = fc; }
-}
-static inline int t748_prof(const t748_state *s, real fe)
-{
-  const real md = ORC_MIN * 32;
-  return fabs(s->fa - s->fb) < md || fabs(s->fa - s->fd) < md || fabs(s->fa - fe) < md ||
-         fabs(s->fb - s->fd) < md || fabs(s->fb - fe) < md || fabs(s->fd - fe) < md;
-}
-static inline real orc_toms748(orc_fn f, void *ctx, real ax, real bx, real fax, real fbx,
-                                 real eps, uintmax_t *max_iter)
-{                                                   /* toms748.hpp:289-431 */
-  uintmax_t count = *max_iter;
-  t748_state s = {ax, bx, fax, fbx, 0, 0};
-  real c, u, fu, a0, b0, e, fe;
-  const real mu = 0.5;
-  if (orc_tol_reached(eps, s.a, s.b) || s.fa == 0 || s.fb == 0) {
-    *max_iter = 0;
-    if (s.fa == 0) s.b = s.a; else if (s.fb == 0) s.a = s.b;
-    return (s.a + s.b) / 2;
-  }
-  fe = e = s.fd = 1e5f;
-  if (s.fa != 0) {
-    c = t748_secant(s.a, s.b, s.fa, s.fb);
-    t748_bracket(f, ctx, &s, c);
-    --count;
-    if (count && s.fa != 0 && !orc_tol_reached(eps, s.a, s.b)) {
-      c = t748_quadratic(s.a, s.b, s.d, s.fa, s.fb, s.fd, 2);
-      e = s.d; fe = s.fd;
-      t748_bracket(f, ctx, &s, c);
-      --count;
-    }
-  }
-  while (count && s.fa != 0 && !orc_tol_reached(eps, s.a, s.b)) {
-    a0 = s.a; b0 = s.b;
-    c = t748_prof(&s, fe) ? t748_quadratic(s.a, s.b, s.d, s.fa, s.fb, s.fd, 2)
-                          : t748_cubic(s.a, s.b, s.d, e, s.fa, s.fb, s.fd, fe);
-    e = s.d; fe = s.fd;
-    t748_bracket(f, ctx, &s, c);
-    if (0 == --count || s.fa == 0 || orc_tol_reached(eps, s.a, s.b)) break;
-    c = t748_prof(&s, fe) ? t748_quadratic(s.a, s.b, s.d, s.fa, s.fb, s.fd, 3)
-                          : t748_cubic(s.a, s.b, s.d, e, s.fa, s.fb, s.fd, fe);
-    t748_bracket(f, ctx, &s, c);
-    if (0 == --count || s.fa == 0 || orc_tol_reached(eps, s.a, s.b)) break;
-    if (fabs(s.fa) < fabs(s.fb)) { u = s.a; fu = s.fa; } else { u = s.b; fu = s.fb; }
-    c = u - 2 * (fu / (s.fb - s.fa)) * (s.b - s.a);
-    if (fabs(c - u) > (s.b - s.a) / 2) c = s.a + (s.b - s.a) / 2;
-    e = s.d; fe = s.fd;
-    t748_bracket(f, ctx, &s, c);
-    if (0 == --count || s.fa == 0 || orc_tol_reached(eps, s.a, s.b)) break;
-    if ((s.b - s.a) < mu * (b0 - a0)) continue;
-    e = s.d; fe = s.fd;
-    t748_bracket(f, ctx, &s, s.a + (s.b - s.a) / 2);
-    --count;
-  }
-  *max_iter -= count;
-  if (s.fa == 0) s.b = s.a; else if (s.fb == 0) s.a = s.b;
-  return (s.a + s.b) / 2;
-}
 
 /* ---- equilibrium wet radius, kappa_koehler.hpp:58-146 ---- */
 typedef struct { real RH, rd3, kappa, T; } rw3eq_ctx;
@@ -272,22 +179,28 @@ static inline real rw3_eq(real rd3, real kappa, real RH, real T)
   return orc_toms748(rw3_eq_minfun, &c, a, b, rw3_eq_minfun(a, &c), rw3_eq_minfun(b, &c), orc_real_eps(), &it);
 }
 
-/* ---- critical radius, kappa_koehler.hpp:88-166.  The reference evaluates it in double whatever real_t is (its products underflow a
- *      float); the float flavour of this file has no double instance of the root finder, so it does not serve the two options that
- *      need rw3_cr (sstp_cond_act > 1, diag_RH_ge_Sc / diag_rw_ge_rc: orc_create refuses them there) ---- */
-typedef struct { real rd3, kappa, T; } rw3cr_ctx;
-static inline real rw3_cr_minfun(real rw3, void *vc)
+/* ---- critical radius, kappa_koehler.hpp:88-166.  The reference evaluates it in double whatever real_t is (rw3_cr_minfun<double>,
+ *      kelvin::A<double>: its products underflow a float), and so does every flavour of this file: the double instance of the root
+ *      finder, and double constants spelled as ratios of integers because the float flavour is compiled with float literals ---- */
+static inline dbl kelvin_A_d(dbl T)
+{
+  const dbl milli = (dbl)1 / 1000, M_v_d = (1 * milli) + (17 * milli), R_v_d = ((dbl)83144621 / 10000000) / M_v_d;
+  const dbl sg = ((dbl)7275 / 100000) * (1 - ((dbl)2 / 1000) * (T - 291));
+  return 2 * sg / R_v_d / T / 1000;
+}
+typedef struct { dbl rd3, kappa, A; } rw3cr_ctx;
+static inline dbl rw3_cr_minfun(dbl rw3, void *vc)
 {
   const rw3cr_ctx *c = (const rw3cr_ctx *)vc;
-  return kelvin_A(c->T) * (c->rd3 - rw3) * ((c->kappa - 1) * c->rd3 + rw3) + 3 * c->kappa * c->rd3 * rw3 * cbrt(rw3);
+  return c->A * (c->rd3 - rw3) * ((c->kappa - 1) * c->rd3 + rw3) + 3 * c->kappa * c->rd3 * rw3 * cbrt(rw3);
 }
 static inline real rw3_cr(real rd3, real kappa, real T)
 {
-  rw3cr_ctx c = {rd3, kappa, T};
-  const real a = 1e0 * rd3, b = 1e8 * rd3;
+  rw3cr_ctx c = {rd3, kappa, kelvin_A_d(T)};
+  const dbl a = (dbl)rd3, b = (dbl)100000000 * (dbl)rd3;
   uintmax_t it = 100;
-  return orc_toms748(rw3_cr_minfun, &c, a, b, rw3_cr_minfun(a, &c), rw3_cr_minfun(b, &c),
-                     orc_eps_tolerance(sizeof(dbl) * 8 / 4), &it);
+  return (real)orc_toms748_d(rw3_cr_minfun, &c, a, b, rw3_cr_minfun(a, &c), rw3_cr_minfun(b, &c),
+                             orc_eps_tolerance_d(sizeof(dbl) * 8 / 4), &it);
 }
 
 /* critical supersaturation, kappa_koehler.hpp:168-189 */

@@ -51,7 +51,7 @@ _oracle = None
 def oracle_lib():
     global _oracle
     if _oracle is None:
-        srcs = [os.path.join(ORACLE_DIR, f) for f in ("lcx_oracle.c", "orc_physics.h", "orc_tables.h")]
+        srcs = [os.path.join(ORACLE_DIR, f) for f in ("lcx_oracle.c", "orc_physics.h", "orc_toms748.h", "orc_tables.h")]
         fm = os.path.join(ORACLE_DIR, "liblcx_oracle_fastmath.so")
         omp = os.path.join(ORACLE_DIR, "liblcx_oracle_omp.so")
         f32 = os.path.join(ORACLE_DIR, "liblcx_oracle_f32.so")

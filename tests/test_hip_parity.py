@@ -641,6 +641,8 @@ def test_incloud_time_matches_oracle():
 
 # ------------------------------------------------------------------ diagnostics (a21)
 def test_diagnostics_match_oracle():
+    # (device against oracle on one even box; the check against a statement that is neither's -- long double, uneven cells, float,
+    #  the edges of the ranges -- lives in tests/test_hip_diagnostics.py)
     oi = h.box_opts(4, 3, 5, 40)
     fields = h.box_fields(oi)
     orc, hip = h.make_pair(oi, fields)
