@@ -364,7 +364,8 @@ int lcx_get_state_u64(lcx_particles *, const char *name, unsigned long long *out
  * "raw_collided" (u64, one value): living super-droplets that carry coalescence's invalid terminal velocity, i.e. the number of pairs that
  * collided in the last lcx_step_async (bench.py's coal-stress workload reports it).  "raw_sorted_id" (u64): the cell-sorted order as the
  * last sort left it -- after a step_sync with condensation, the shuffled order that the step's coalescence will pair up (an error while
- * the re-sort is still deferred). */
+ * the re-sort is still deferred).  "raw_coal_kernel" (u64, one value): the coalescence kernel of the last launch -- 0 the generic one,
+ * 1 the one with the Onishi kernel, 2 the production variant (tabulated efficiencies, the library's own random numbers, fused step). */
 int lcx_get_state_real(lcx_particles *, const char *name, double *out, size_t cap, size_t *n);
 /* overwrite particle state (all arrays of length n; x/y/z may be NULL for absent dimensions);
  * lets a test start the device from an oracle state */

@@ -1607,6 +1607,7 @@ struct Particles : IParticles {
   // the previous coalescence substep has left velocities invalid: the in-cell ranking of the next one refreshes them on its way
   // (order_cells), or the pass of its own does where another ranking kernel runs
   bool vt_fix_pending = false;
+  int last_coal_kernel = 0;                  // (the k_coal variant of the last launch, "raw_coal_kernel": 0 generic, 1 Onishi, 2 production)
   void coal(double dt_sub, bool turb_coal = false)
   {
     if (!replay.empty()) ensure_compact();     // un[id] of a replayed CPU stream is indexed by the reference's (compact) ids
@@ -1626,10 +1627,10 @@ struct Particles : IParticles {
                          ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr);
     };
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
-    if (onishi) launch(k_coal<T, true>);
+    if (onishi) { last_coal_kernel = 1; launch(k_coal<T, true>); }
     // (the production kernel writes the collision record only for the kappa pass: nothing else reads it outside a replayed run)
-    else if (tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead) launch(k_coal<T, false, true>, kappa_pass || chem_pass);
-    else launch(k_coal<T, false>);
+    else if (tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead) { last_coal_kernel = 2; launch(k_coal<T, false, true>, kappa_pass || chem_pass); }
+    else { last_coal_kernel = 0; launch(k_coal<T, false>); }
     if (kappa_pass)
       hipLaunchKernelGGL(k_coal_kappa<T>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sid(), col.p, A.kpa.p, A.rd3.p);
     if (chem_pass)                                                                       // coal.ipp:458-480
@@ -2668,6 +2669,7 @@ struct Particles : IParticles {
     else if (s == "raw_mode") {                    // what this object runs: strict_fp, cond_solver, the kernel of its last condensation launch (enum lcx_cond_kernel), dbg_flags
       v = {(unsigned long long)(o.strict_fp ? 1 : 0), (unsigned long long)o.cond_solver, (unsigned long long)last_cond_kernel, (unsigned long long)o.dbg_flags};
     }
+    else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
       unsigned long long c = 0;
       if (defer_cnt.p && defer_cnt.n >= size_t(DEFER_SHARDS * DEFER_CNT_STRIDE) && o.cond_solver == 0) {

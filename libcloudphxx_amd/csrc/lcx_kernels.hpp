@@ -2366,6 +2366,11 @@ __device__ T wang_collision_enhancement(T r1, T r2, T eps)
   for (n_R0 = 0; n_R0 < 7; ++n_R0) if (R0[n_R0] > R) break;
   const T ratio = r / R;
   for (n_rat = 1; n_rat < 11; ++n_rat) if (rat[n_rat] > ratio) break;
+  // The reference leaves n_rat == 11 at ratio == 1 (equal radii) and n_R0 == 7 at R == 100e-6 and reads past eta_e, rat and R0 there
+  // (undefined behaviour).  Clamped: w3 == 0 then gives row 10, w1 == 0 gives column 6 (1.0) -- the continuous limits of what it
+  // computes just beside.
+  if (n_rat > 10) n_rat = 10;
+  if (n_R0 > 6) n_R0 = 6;
   if (n_R0 == 0) return T(wang_eta_e[n_rat][n_eps][n_R0]);
   const T w0 = R - R0[n_R0 - 1], w1 = R0[n_R0] - R, w2 = ratio - rat[n_rat - 1], w3 = rat[n_rat] - ratio;
   return (T(wang_eta_e[n_rat - 1][n_eps][n_R0 - 1]) * w1 * w3 + T(wang_eta_e[n_rat - 1][n_eps][n_R0]) * w0 * w3 +

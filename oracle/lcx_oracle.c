@@ -1032,7 +1032,7 @@ static real k_geometric(n_t na, n_t nb, real rw2a, real rw2b, real vta, real vtb
    reproduced, the results are what the reference produces. */
 static real kernel_onishi_nograv(real r1, real r2, real Re_l, real eps, real dnu, real ratio_den)
 {
-  if (eps < 1e-10) return 0.;
+  if ((dbl)eps < (dbl)1 / 10000000000) return 0.;      /* (a real_t against the literal 1e-10: double in the reference whatever real_t is) */
   const real urms = sqrt(Re_l / sqrt(15. / dnu / eps));
   const real CR = r1 + r2;
   const real taup1 = ratio_den * 4. * r1 * r1 / 18. / dnu, taup2 = ratio_den * 4. * r2 * r2 / 18. / dnu;
@@ -1094,12 +1094,18 @@ static real wang_collision_enhancement(real r1, real r2, real eps)
     {{1.570, 1.570, 1.244, 1.166, 1.088, 1.088, 1.0}, {3.788, 3.788, 1.501, 1.311, 1.120, 1.120, 1.0}},
     {{20.3, 20.3, 14.6, 8.61, 2.60, 2.60, 1.0}, {36.52, 36.52, 19.16, 22.80, 26.0, 26.0, 1.0}}};
   const real R = r1 > r2 ? r1 : r2, r = r1 > r2 ? r2 : r1;
-  if (R > 100e-6) return 1.;
-  const int n_eps = eps <= 2.5e-2 ? 0 : 1;
+  /* real_t against the literals 100e-6 and 2.5e-2: the reference compares in double whatever real_t is (the float flavour's literals
+     are float, so the double ones are spelled as ratios of integers) */
+  if ((dbl)R > (dbl)100 / 1000000) return 1.;
+  const int n_eps = (dbl)eps <= (dbl)25 / 1000 ? 0 : 1;
   int n_R0, n_rat;
   for (n_R0 = 0; n_R0 < 7; ++n_R0) if (R0[n_R0] > R) break;
   const real ratio = r / R;
   for (n_rat = 1; n_rat < 11; ++n_rat) if (rat[n_rat] > ratio) break;
+  /* the reference runs off its arrays at ratio == 1 (n_rat == 11) and R == 100e-6 (n_R0 == 7): clamped to the continuous limits,
+     row 10 (w3 == 0) and column 6 (w1 == 0), as the product does */
+  if (n_rat > 10) n_rat = 10;
+  if (n_R0 > 6) n_R0 = 6;
   if (n_R0 == 0) return eta_e[n_rat][n_eps][n_R0];
   const real w0 = R - R0[n_R0 - 1], w1 = R0[n_R0] - R, w2 = ratio - rat[n_rat - 1], w3 = rat[n_rat] - ratio;
   return (eta_e[n_rat - 1][n_eps][n_R0 - 1] * w1 * w3 + eta_e[n_rat - 1][n_eps][n_R0] * w0 * w3 +
@@ -1130,9 +1136,9 @@ static real kernel_calc(const orc_particles *s, n_t na, n_t nb, real rw2a, real 
     case LCX_KERNEL_LONG: {
       real res = k_geometric(na, nb, rw2a, rw2b, vta, vtb);
       const real r_L = dmax(sqrt(rw2a), sqrt(rw2b));
-      if (r_L < 50.e-6) {
+      if ((dbl)r_L < (dbl)50 / 1000000) {          /* (50.e-6 and 3e-6 are double literals in the reference: compared in double) */
         const real r_s = dmin(sqrt(rw2a), sqrt(rw2b));
-        if (r_s <= 3e-6) res = 0.; else res *= 4.5e8 * r_L * r_L * (1. - 3e-6 / r_s);
+        if ((dbl)r_s <= (dbl)3 / 1000000) res = 0.; else res *= 4.5e8 * r_L * r_L * (1. - 3e-6 / r_s);
       }
       return res;
     }

@@ -137,6 +137,8 @@ def test_big_segment_sort_0d():
 
 
 # ------------------------------------------------------------------ terminal velocity (a6)
+# (device against oracle, one arithmetic, one even n_part.  Against a long-double statement of the formulas, at the regime boundaries,
+#  odd tails and workgroup edges, in every arithmetic: tests/_vterm_coal_reference.py, test_oracle_vterm_coal.py, test_hip_vterm_coal.py)
 @pytest.mark.parametrize("vt", [lgrngn.vt_t.beard76, lgrngn.vt_t.beard77, lgrngn.vt_t.beard77fast,
                                 lgrngn.vt_t.khvorostyanov_spherical, lgrngn.vt_t.khvorostyanov_nonspherical])
 def test_vterm(vt):
