@@ -222,6 +222,8 @@ enum lcx_dbg {
                                         * next substep's in-cell ranking (the same bits) */
   LCX_DBG_RLX_GLOBAL_ATOMICS = 1 << 29, /* aerosol relaxation, measured and not adopted (5 x slower; the tests' cross-check of the census table): the census as one pass in storage order with a global 64-bit atomic
                                         * per counted droplet (k_rlx_census_global) instead of the per-level table in LDS (the same counts) */
+  LCX_DBG_NO_RANK_IN_COAL = 1 << 30,   /* the in-cell shuffled order of a carried re-sort ranked by a kernel of its own and written to memory (rounds 1-6) instead of
+                                        * inside the coalescence kernel that consumes it (k_coal_ranked: the same bits; "raw_coal_ranked") */
   LCX_DBG_COND_TOMS_TWO_PASS = 1 << 15 /* cond_solver = 1 through round 2's kernels (k_cond_fast_fold + k_cond_fast over the sorted order, iteration budget and
                                         * straggler launch) instead of the storage-order kernel with TOMS748 in it */
 };
@@ -365,7 +367,10 @@ int lcx_get_state_u64(lcx_particles *, const char *name, unsigned long long *out
  * collided in the last lcx_step_async (bench.py's coal-stress workload reports it).  "raw_sorted_id" (u64): the cell-sorted order as the
  * last sort left it -- after a step_sync with condensation, the shuffled order that the step's coalescence will pair up (an error while
  * the re-sort is still deferred).  "raw_coal_kernel" (u64, one value): the coalescence kernel of the last launch -- 0 the generic one,
- * 1 the one with the Onishi kernel, 2 the production variant (tabulated efficiencies, the library's own random numbers, fused step). */
+ * 1 the one with the Onishi kernel, 2 the production variant (tabulated efficiencies, the library's own random numbers, fused step).
+ * "raw_coal_ranked" (u64, one value): how many coalescence launches of the last lcx_step_async ranked their cells' shuffled order for
+ * themselves (k_coal_ranked: the first substep at most); 0: each read an order that a ranking kernel had written to memory (reading
+ * "raw_sorted_id" ahead of the step, crowded cells or LCX_DBG_NO_RANK_IN_COAL make it so). */
 int lcx_get_state_real(lcx_particles *, const char *name, double *out, size_t cap, size_t *n);
 /* overwrite particle state (all arrays of length n; x/y/z may be NULL for absent dimensions);
  * lets a test start the device from an oracle state */

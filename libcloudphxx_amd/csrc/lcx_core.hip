@@ -313,7 +313,23 @@ struct Particles : IParticles {
   // scan that rewrites cell_start, a host synchronisation -- makes `st` wait for the ranking first (join_rank): ordered by construction.
   hipStream_t st_rank = nullptr; hipEvent_t ev_fork = nullptr, ev_rank = nullptr; mutable bool rank_pending = false;
   void join_rank() const { if (rank_pending) { rank_pending = false; HIPCHK(hipStreamWaitEvent(st, ev_rank, 0)); } }
-  uint32_t *sid() const { join_rank(); return sorted_id.p + sort_base; }
+  // The shuffled in-cell order of a carried re-sort may be OWED instead of made (rank_owed): the scatter has left every cell's ids in arrival
+  // order, the flags (sorted, sorted_shuffled, shuffle_fresh) say what the order will be once ranked with the salts deferred_rs, and nothing
+  // has been launched.  The production coalescence kernel ranks for itself in LDS (k_coal_ranked, coal()) and needs no order in memory; whoever
+  // else reads the in-cell order goes through sid(), which makes it first (pay_rank: today's order_cells, on the main stream, into a buffer
+  // of its own -- `rank` may hold the next sort's arrival ranks by then).  The debt is void once cell_start is rewritten or the cells are
+  // ranked anew (order_cells).  sijk() and cell_start do not depend on the in-cell order and need nothing.
+  bool rank_owed = false; DevBuf<uint32_t> rank_paid;
+  void pay_rank()
+  {
+    if (!rank_owed) return;
+    rank_owed = false;
+    Range r(this, "post_copy");
+    const bool fresh = shuffle_fresh;                  // (the flags already describe the order that is being made)
+    order_cells(deferred_shuffle, &deferred_rs, true);
+    shuffle_fresh = fresh;
+  }
+  uint32_t *sid() { pay_rank(); join_rank(); return sorted_id.p + sort_base; }
   uint32_t *sijk() const { join_rank(); return sorted_ijk.p + sort_base; }
   uint32_t *rnk() const { join_rank(); return rank.p; }
   DevBuf<uint8_t> mig, cond_pre, wave_flag, cond_records; DevBuf<uint32_t> defer_cnt, wg_mig, cond_listed;
@@ -885,7 +901,7 @@ struct Particles : IParticles {
       hipLaunchKernelGGL(k_ijk_hist<T>, dim3(nblk(nphys)), dim3(BS), 0, st, size_t(0), nphys, g, A.n.p, A.x.p, A.y.p, A.z.p, ijk.p,
                          do_hist ? cell_cnt.p : nullptr, rnk(), do_ijk);
   }
-  void hskpng_ijk() { Range r(this, "hskpng_ijk"); ijk_and_hist(2, false); sorted = false; sort_deferred = false; }   // (a sort left undone is void)
+  void hskpng_ijk() { Range r(this, "hskpng_ijk"); ijk_and_hist(2, false); sorted = false; sort_deferred = false; rank_owed = false; }   // (a sort left undone is void)
   // finish a sort given cell_cnt/rank: scan -> scatter -> per-cell order
   // meta_known: {number of cells above CELLRANK_MAX, largest occupancy} already on the host (listed from the histogram ahead of the
   // step's read-back), else order_cells lists them from the CSR offsets and pays a host round trip of its own
@@ -907,7 +923,7 @@ struct Particles : IParticles {
   const bool defer_sort_ok = !dbg(LCX_DBG_NO_DEFERRED_SORT);
   void sort_from_hist(bool shuffle, const uint32_t *meta_known = nullptr, bool defer = false)
   {
-    sort_deferred = false;
+    sort_deferred = false; rank_owed = false;           // (cell_start is rewritten: an order still owed is void)
     // (the scan leaves the histogram and the step's counters cleared for the next fused move)
     exclusive_scan(cell_cnt.p, cell_start.p, ncell, cell_start.p + ncell, cell_cnt.p, step_cnt.p, 3);
     ++cells_version;
@@ -934,9 +950,12 @@ struct Particles : IParticles {
     shuffle_fresh = deferred_shuffle;
   }
   // puts every cell segment of sorted_id into the reference's order: ascending id, or ascending (un[id], id)
-  void order_cells(bool shuffle, const rng_src *drawn = nullptr)
+  // spare: the ranking's output goes to a buffer of its own instead of `rank` (pay_rank)
+  void order_cells(bool shuffle, const rng_src *drawn = nullptr, bool spare = false)
   {
-    sort_deferred = false;
+    sort_deferred = false; rank_owed = false;          // (every cell is ranked anew, from whatever order it is in)
+    if (spare) rank_paid.alloc(cap + sort_headroom);
+    DevBuf<uint32_t> &out_buf = spare ? rank_paid : rank;
     if (npart) {
       rng_src rs{nullptr, 0, 0, 0u, 0u};
       if (drawn) rs = *drawn;
@@ -954,20 +973,21 @@ struct Particles : IParticles {
         }
         const int crowded = npart / (ncell ? ncell : 1) > size_t(CELLRANK_MAX) / 2;
         if (every_cell_by_a_wave()) ;           // every cell is sorted in place below: nothing to rank and no buffer swap
-        else if (shuffle && !rs.un && !crowded && !shuffle_philox && (rs.s1 | rs.s2) && !dbg(LCX_DBG_RANK_BY_COUNTING) && vt_fix_pending && nphys) {
-          // (between two coalescence substeps: hskpng_vterm_invalid rides on the ranking, see step_async)
+        else if (shuffle && !rs.un && !crowded && !shuffle_philox && (rs.s1 | rs.s2) && !dbg(LCX_DBG_RANK_BY_COUNTING) && vt_fix_pending && nphys &&
+                 (!(vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST) || vtpre_valid)) {
+          // (between two coalescence substeps: hskpng_vterm_invalid rides on the ranking, see step_async; beard77 needs its cell part, vt_pre)
           const bool b77 = vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST;
           const rank_vt_fix<T> fx{vtc, b77 ? (vtc.formula == LCX_VT_BEARD77FAST ? 2 : 1) : 0, o.strict_fp ? 0 : 1, Tk.p, p.p, rhod.p, eta.p, vt_0.p,
                                   b77 ? vt_pre.p : nullptr, A.rw2.p, A.vt.p};
-          hipLaunchKernelGGL((k_cellrank_bkt<true, rank_vt_fix<T>>), dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), rnk() + sort_base, rs,
+          hipLaunchKernelGGL((k_cellrank_bkt<true, rank_vt_fix<T>>), dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), (join_rank(), out_buf.p) + sort_base, rs,
                              rank_range{nullptr, nullptr, nullptr}, fx);
           vt_fix_pending = false;
         }
-        else if (shuffle && !rs.un && !crowded && !shuffle_philox && (rs.s1 | rs.s2) && !dbg(LCX_DBG_RANK_BY_COUNTING)) hipLaunchKernelGGL(k_cellrank_bkt<>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), rnk() + sort_base, rs, rank_range{nullptr, nullptr, nullptr});
-        else if (shuffle && !rs.un && !crowded && !shuffle_philox) hipLaunchKernelGGL((k_cellrank<uint32_t, true>), dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), rnk() + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
-        else if (shuffle) hipLaunchKernelGGL(k_cellrank<uint64_t>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), rnk() + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
-        else hipLaunchKernelGGL(k_cellrank<uint32_t>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), rnk() + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
-        if (!every_cell_by_a_wave()) sorted_id.swap(rank);        // `rank` is free after the scatter: it serves as the output buffer
+        else if (shuffle && !rs.un && !crowded && !shuffle_philox && (rs.s1 | rs.s2) && !dbg(LCX_DBG_RANK_BY_COUNTING)) hipLaunchKernelGGL(k_cellrank_bkt<>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), (join_rank(), out_buf.p) + sort_base, rs, rank_range{nullptr, nullptr, nullptr});
+        else if (shuffle && !rs.un && !crowded && !shuffle_philox) hipLaunchKernelGGL((k_cellrank<uint32_t, true>), dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), (join_rank(), out_buf.p) + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
+        else if (shuffle) hipLaunchKernelGGL(k_cellrank<uint64_t>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), (join_rank(), out_buf.p) + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
+        else hipLaunchKernelGGL(k_cellrank<uint32_t>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sijk(), cell_start.p, sid(), (join_rank(), out_buf.p) + sort_base, rs, crowded, rank_range{nullptr, nullptr, nullptr});
+        if (!every_cell_by_a_wave()) sorted_id.swap(out_buf);     // `rank` is free after the scatter: it serves as the output buffer
         if (meta_version != cells_version) {
           uint32_t m2[2];
           read_back(m2, big_meta_own_p(), 2);
@@ -1448,7 +1468,12 @@ struct Particles : IParticles {
     if (carry_scatter) {                                      // the in-cell ranking, behind the kernel that scattered
       // (on its own stream when the list of crowded cells is on the host already, i.e. nothing in it waits for the device)
       // (not while every stage is being timed, lcx_set_profiling(1): the stage table is of stages that run one after the other)
-      if (!dbg(LCX_DBG_NO_RANK_OVERLAP) && profiling != 1 && meta_version == cells_version) {
+      if (!dbg(LCX_DBG_NO_RANK_OVERLAP) && profiling != 1 && meta_version == cells_version && coal_will_rank()) {
+        // nothing is launched: the step's coalescence ranks for itself, any other reader makes the order first (rank_owed, above sid())
+        sort_deferred = false; rank_owed = true;
+        sorted = true; sorted_shuffled = true; shuffle_fresh = true; last_shuffle_rs = deferred_rs;
+      }
+      else if (!dbg(LCX_DBG_NO_RANK_OVERLAP) && profiling != 1 && meta_version == cells_version) {
         if (!st_rank) {
           HIPCHK(hipStreamCreateWithFlags(&st_rank, hipStreamNonBlocking));
           HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_rank, hipEventDisableTiming));
@@ -1607,16 +1632,54 @@ struct Particles : IParticles {
   // the previous coalescence substep has left velocities invalid: the in-cell ranking of the next one refreshes them on its way
   // (order_cells), or the pass of its own does where another ranking kernel runs
   bool vt_fix_pending = false;
+  // k_coal_ranked: what of the object's options the kernel serves (the production configuration: a tabulated kernel, the library's own random
+  // numbers and salted shuffle keys, one hygroscopicity, no chemistry, no per-droplet extras, one device) ...
+  bool coal_ranks_config() const
+  {
+    const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
+    const bool onishi = o.kernel == LCX_KERNEL_ONISHI_HALL || o.kernel == LCX_KERNEL_ONISHI_HALL_DAVIS_NO_WAALS;
+    return !dbg(LCX_DBG_NO_RANK_IN_COAL) && !dbg(LCX_DBG_RANK_BY_COUNTING) && !shuffle_philox && o.coal_switch && tabulated && !onishi && !pure_const_multi &&
+           !use_rc2 && ix_ict < 0 && ix_tag < 0 && o.n_dry_distros + n_size_keys <= 1 && !o.chem_switch && !distmem() && n_dims > 0 && replay.empty();
+  }
+  // ... and of the order that is owed: a shuffle on salted keys, no cell above CELLRANK_MAX (the kernel's window holds every touched cell)
+  bool cells_rankable() const { return meta_version == cells_version && big_n == 0 && !every_cell_by_a_wave() && npart >= 2; }
+  bool owed_order_rankable() const { return deferred_shuffle && !deferred_rs.un && (deferred_rs.s1 | deferred_rs.s2) && cells_rankable(); }
+  // cond_substep: is the order worth owing?  (Where the coalescence of this step will not take it -- none ran in the last step, or another
+  // kernel will -- the ranking runs beside the per-cell finish as before instead of on the main stream later.)
+  bool coal_will_rank() const { return coal_ranks_config() && owed_order_rankable() && last_async_coal; }
+  int last_coal_ranked = 0;                  // ("raw_coal_ranked": the coalescence launches of the last step_async that ranked for themselves)
   int last_coal_kernel = 0;                  // (the k_coal variant of the last launch, "raw_coal_kernel": 0 generic, 1 Onishi, 2 production)
-  void coal(double dt_sub, bool turb_coal = false)
+  void coal(double dt_sub, bool turb_coal = false, bool first_substep = true)
   {
     if (!replay.empty()) ensure_compact();     // un[id] of a replayed CPU stream is indexed by the reference's (compact) ids
-    hskpng_sort_helper(true);
+    finish_deferred_sort();
+    if (first_substep && sorted && !(sorted_shuffled && shuffle_fresh) && coal_ranks_config() && cells_rankable()) {
+      // cells unchanged since the last sort, no shuffle made ahead (the first step of a run, a step whose re-sort was not carried): the
+      // shuffle that hskpng_sort_helper would launch is owed as well -- the salts drawn now, at their place in the generator's sequence
+      deferred_shuffle = true; deferred_rs = rand_un(npart); last_shuffle_rs = deferred_rs;
+      rank_owed = true; sorted_shuffled = true; shuffle_fresh = false;
+      if (!owed_order_rankable()) pay_rank();          // (both salts zero: the Philox keys, ranked on 64 bits)
+    }
+    else hskpng_sort_helper(true);
     if (vt_fix_pending) { vt_fix_pending = false; hskpng_vterm(true); }
     if (npart < 2) { if (npart) (void)rand_u01(npart); return; }
     Range r(this, "coal");
     const u01_src<T> rs = rand_u01(npart);
     if (ix_tag >= 0) record_rng(rs);
+    // The order this coalescence pairs up is still owed (hskpng_sort_helper has found it `fresh` and ranked nothing): the kernel that ranks
+    // for itself takes the cells as the scatter left them.  The debt stays -- sorted_id in memory is in arrival order -- until somebody
+    // reads the order (pay_rank) or the step's re-sort makes it void.
+    if (rank_owed && first_substep && coal_ranks_config() && owed_order_rankable() && sorted && sorted_shuffled && !rs.arr) {
+      coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
+      const dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));
+      last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
+                           deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr);
+      };
+      if (coal_marks_dead) launch(k_coal_ranked<T, true>); else launch(k_coal_ranked<T, false>);
+      return;
+    }
     const bool onishi = o.kernel == LCX_KERNEL_ONISHI_HALL || o.kernel == LCX_KERNEL_ONISHI_HALL_DAVIS_NO_WAALS;
     // diss == nullptr stands for the reference's constant-zero dissipation rate when opts.turb_coal is off (coal.ipp:392-403,439-451)
     coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
@@ -2286,7 +2349,7 @@ struct Particles : IParticles {
     hskpng_vterm(true);
     hskpng_approximate_rc2_invalid();                                                    // particles_init.ipp:116-117
     sstp_save();
-    sorted = false; sort_deferred = false;
+    sorted = false; sort_deferred = false; rank_owed = false;
     hskpng_count();
     if (!B.n.p) alloc_attrs(B);      // the compaction target: allocated here, not inside the first step that compacts (GBs of hipMalloc)
     sync();
@@ -2466,6 +2529,8 @@ struct Particles : IParticles {
     const bool rlx_now = opts.rlx && rlx_fires();
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
+    last_coal_ranked = 0;
+    vt_fix_pending = false;                           // (a flag of one step_async: nothing of an earlier call is pending)
     last_async_coal = opts.coal != 0;
     coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
                                                        // substeps a used-up SD still takes part in the later ones and keeps its cell)
@@ -2473,7 +2538,7 @@ struct Particles : IParticles {
     if (opts.sedi || opts.coal || opts.cond) hskpng_vterm(false);
     if (opts.coal) {
       for (int step = 0; step < sstp_coal; ++step) {
-        coal(dt / sstp_coal, opts.turb_coal);
+        coal(dt / sstp_coal, opts.turb_coal, step == 0);
         // (hskpng_vterm_invalid between the substeps: left to the next substep's ranking, which every droplet passes anyway)
         if (step + 1 != sstp_coal) { if (dbg(LCX_DBG_VTERM_INVALID_OWN_PASS)) hskpng_vterm(true); else vt_fix_pending = true; }
       }
@@ -2495,6 +2560,9 @@ struct Particles : IParticles {
     if (rlx_now) rlx_census_and_plan();              // (on the cells of the step's start, before the move rewrites ijk)
     const size_t n_chem_pud = o.chem_switch && n_dims > 1 && !o.periodic_topbot_walls ? nphys : 0;
     if (n_chem_pud) { chem_n_before.alloc(cap); HIPCHK(hipMemcpyAsync(chem_n_before.p, A.n.p, n_chem_pud * sizeof(n_t), hipMemcpyDeviceToDevice, st)); }
+    // an order still owed: void where the step ends in the fused move and its re-sort with nothing in between that reads the old order (the
+    // move writes the next sort's arrival ranks); made now otherwise
+    if (rank_owed) { if (fused && !distmem() && !src_now && !rlx_now) rank_owed = false; else pay_rank(); }
     move(opts.adve, opts.sedi, opts.subs, true, fused);
     if (n_chem_pud) chem_puddle_add(n_chem_pud);
     hold_big_list = false;
@@ -2669,6 +2737,7 @@ struct Particles : IParticles {
     else if (s == "raw_mode") {                    // what this object runs: strict_fp, cond_solver, the kernel of its last condensation launch (enum lcx_cond_kernel), dbg_flags
       v = {(unsigned long long)(o.strict_fp ? 1 : 0), (unsigned long long)o.cond_solver, (unsigned long long)last_cond_kernel, (unsigned long long)o.dbg_flags};
     }
+    else if (s == "raw_coal_ranked") v.assign(1, (unsigned long long)last_coal_ranked);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
       unsigned long long c = 0;

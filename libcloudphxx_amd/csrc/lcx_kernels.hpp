@@ -2435,22 +2435,15 @@ template <class T> struct u01_src { const T *arr; uint64_t call, seed; };
 // gathered ONCE into LDS (24 B per droplet) and the pairs served from there -- the same droplets bit for bit, and 16.1 ms against
 // 14.2 on C5: the L1 already spares the L2 most of the repeated lines, and 2.1e6 workgroups that each wait at a barrier behind their
 // gathers are slower than the walk's independent lanes.)
-template <class T, bool ONISHI, bool TAB = false>
-__global__ void __launch_bounds__(BS)
-k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, const uint32_t *cell_start,
-       n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs,
-       int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
+// the pair that the lane looking at position p0 owns, given the cells (c0, c1, c2) and ids (i0, i1, i2) of the positions p0, p0 + 1, p0 + 2 and
+// the CSR bounds of the first two cells: the body of k_coal, shared with the kernel that ranks the cells for itself (k_coal_ranked)
+template <class T, bool ONISHI>
+__device__ __forceinline__ void
+coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t i0, const uint32_t i1, const uint32_t i2,
+          const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1,
+          n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
+          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
 {
-  if (TAB) { kc.kernel = LCX_KERNEL_HALL; pure_const_multi = 0; rs.arr = nullptr; rc2 = nullptr; ict = nullptr; __builtin_assume(ijk_mark != nullptr); }
-  const size_t p0 = 2 * gid();
-  if (p0 + 1 >= n_part) return;                       // the reference's range is [0, n_part-1)
-  // The three positions a lane may need (2t, 2t+1, 2t+2) and the CSR bounds of their first two cells are fetched up front, in two
-  // dependent levels; then the pair's attributes in one batch.  (Written as the decision tree reads, the kernel walked six or seven
-  // dependent loads, and 70 % of its wave-cycles were waits.)
-  const bool has2 = p0 + 2 < n_part;
-  const uint32_t c0 = sorted_ijk[p0], c1 = sorted_ijk[p0 + 1], c2 = has2 ? sorted_ijk[p0 + 2] : DEAD_CELL;
-  const uint32_t i0 = sorted_id[p0], i1 = sorted_id[p0 + 1], i2 = has2 ? sorted_id[p0 + 2] : 0u;
-  const uint32_t off0 = cell_start[c0], end0 = cell_start[c0 + 1], off1 = cell_start[c1], end1 = cell_start[c1 + 1];
   size_t p = p0;
   uint32_t ca = c0, off = off0, end = end0, a = i0, b = i1;
   {
@@ -2502,6 +2495,133 @@ k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, con
     if (col) col[p + 1] = T(-1);
   }
   if (col) col[p] = T(col_no);
+}
+template <class T, bool ONISHI, bool TAB = false>
+__global__ void __launch_bounds__(BS)
+k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, const uint32_t *cell_start,
+       n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs,
+       int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
+{
+  if (TAB) { kc.kernel = LCX_KERNEL_HALL; pure_const_multi = 0; rs.arr = nullptr; rc2 = nullptr; ict = nullptr; __builtin_assume(ijk_mark != nullptr); }
+  const size_t p0 = 2 * gid();
+  if (p0 + 1 >= n_part) return;                       // the reference's range is [0, n_part-1)
+  // The three positions a lane may need (2t, 2t+1, 2t+2) and the CSR bounds of their first two cells are fetched up front, in two
+  // dependent levels; then the pair's attributes in one batch.  (Written as the decision tree reads, the kernel walked six or seven
+  // dependent loads, and 70 % of its wave-cycles were waits.)
+  const bool has2 = p0 + 2 < n_part;
+  const uint32_t c0 = sorted_ijk[p0], c1 = sorted_ijk[p0 + 1], c2 = has2 ? sorted_ijk[p0 + 2] : DEAD_CELL;
+  const uint32_t i0 = sorted_id[p0], i1 = sorted_id[p0 + 1], i2 = has2 ? sorted_id[p0 + 2] : 0u;
+  const uint32_t off0 = cell_start[c0], end0 = cell_start[c0 + 1], off1 = cell_start[c1], end1 = cell_start[c1 + 1];
+  coal_pair<T, ONISHI>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, col, dv, dt, kc, rs, pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark);
+}
+// Round 7: the production coalescence RANKING EACH CELL'S ORDER FOR ITSELF.  k_cellrank_bkt wrote the shuffled order to memory for this kernel
+// alone to read back (17 B per super-droplet and step).  Here a workgroup owns the 2 BS positions [P0, P0 + 2 BS) of the cell-sorted order as
+// the scatter left it (inside a cell: arrival order), stages the keys shuffle_un(id, s1, s2) of every cell those positions -- and P0 + 2 BS,
+// the third position of its last lane -- touch, ranks them by k_cellrank_bkt's bucket method and keeps the ranked IDS of its own positions
+// in LDS; behind one more barrier every lane runs coal_pair with the ids of 2t, 2t + 1, 2t + 2 served from there.  A pair's two members lie
+// in one cell and every touched cell is staged whole, so every id a lane needs is there.  The keys are unique: the order is the one that
+// k_cellrank_bkt (or any other ranking) gives, hence the same pairs, the same random number by position, the same bits.
+// Every lane takes the four entries P0 - BS + t + k BS (k = 0 ... 3) of the window [P0 - BS, P0 + 3 BS): k = 1, 2 are its two own positions,
+// k = 0 lies in the first cell and k = 3 in the last one wherever they are staged, so only the own positions look their cells up.  The host
+// launches this kernel only where no cell is above CELLRANK_MAX (= BS) droplets, and then the window holds every touched cell.  Should it
+// not -- or the range not fit the stage -- the workgroup ranks by counting in memory (correct for any cell size, slow).
+// The barriers all sit AHEAD of the attribute gathers (see the LDS form that lost, above k_coal: workgroups waiting behind their gathers).
+constexpr int COAL_RANKED_POS = 2 * BS;
+// MARK: used-up super-droplets are marked in ijk (the step ends in the fused move), as in k_coal<T, false, true>
+template <class T, bool MARK>
+__global__ void __launch_bounds__(BS)
+k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
+              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark)
+{
+  using KEY = uint32_t;
+  constexpr int CAP = 4 * BS, OWN = COAL_RANKED_POS;
+  static_assert(CAP == cr_cap<KEY>, "four counters per lane in the scan");
+  __shared__ KEY lds[CAP];                 // the keys grouped by bucket
+  __shared__ uint32_t bkt[CAP];            // bucket counts, then their exclusive prefix sums
+  __shared__ uint32_t ids[OWN + 4];        // the ranked ids of the positions [P0, P0 + OWN]
+  __shared__ uint32_t bounds[4];
+  __shared__ uint32_t wsum[BS / WAVE];
+  kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
+  if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
+  const size_t P0 = size_t(blockIdx.x) * OWN;
+  if (P0 + 1 >= n_part) return;                        // (uniform)
+  const uint32_t t = threadIdx.x;
+  const size_t p0 = P0 + 2 * t;
+  const bool pair_lane = p0 + 1 < n_part, has2 = p0 + 2 < n_part;
+  // what coal_pair needs of the cells, fetched up front as in k_coal
+  uint32_t c0 = 0, c1 = 0, c2 = DEAD_CELL, off0 = 0, end0 = 0, off1 = 0, end1 = 0;
+  if (pair_lane) { c0 = sorted_ijk[p0]; c1 = sorted_ijk[p0 + 1]; if (has2) c2 = sorted_ijk[p0 + 2]; }
+  const size_t last = (P0 + OWN < n_part ? P0 + OWN + 1 : n_part) - 1;       // the last position whose id a lane of this workgroup may need
+  // the four entries of the window
+  const size_t q1 = P0 + t, q2 = P0 + BS + t, q3 = P0 + 2 * BS + t;
+  const bool in0 = P0 + t >= size_t(BS), in1 = q1 < n_part, in2 = q2 < n_part, in3 = last == P0 + OWN && q3 < n_part;
+  const size_t q0 = in0 ? P0 + t - BS : 0;
+  uint32_t id0 = 0, id1 = 0, id2 = 0, id3 = 0, s1 = 0, e1 = 0, s2 = 0, e2 = 0;
+  if (in0) id0 = in[q0];
+  if (in3) id3 = in[q3];
+  if (in1) { const uint32_t c = sorted_ijk[q1]; id1 = in[q1]; s1 = cell_start[c]; e1 = cell_start[c + 1]; }
+  if (in2) { const uint32_t c = sorted_ijk[q2]; id2 = in[q2]; s2 = cell_start[c]; e2 = cell_start[c + 1]; }
+  if (t == WAVE) { const uint32_t c = sorted_ijk[last]; bounds[1] = cell_start[c + 1]; bounds[3] = cell_start[c]; }   // (a wave that does not also hold lane 0)
+  if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
+#pragma unroll
+  for (int k = 0; k < CAP / BS; ++k) bkt[t + k * BS] = 0u;
+  const KEY key0 = shuffle_un(id0, r.s1, r.s2), key1 = shuffle_un(id1, r.s1, r.s2), key2 = shuffle_un(id2, r.s1, r.s2), key3 = shuffle_un(id3, r.s1, r.s2);
+  if (t == 0) { bounds[0] = s1; bounds[2] = e1; }      // (position P0 exists: P0 + 1 < n_part)
+  __syncthreads();
+  const uint32_t lo = bounds[0], hi = bounds[1], e_first = bounds[2], s_last = bounds[3];
+  const uint32_t m = hi - lo;
+  const bool by_buckets = m <= uint32_t(CAP) && size_t(lo) + BS >= P0 && size_t(hi) <= P0 + 3 * size_t(BS);
+  if (by_buckets) {
+    const bool v0 = in0 && q0 >= lo, v1 = in1, v2 = in2, v3 = in3 && q3 < hi;
+    uint32_t bi0 = 0, bi1 = 0, bi2 = 0, bi3 = 0, sl0 = 0, sl1 = 0, sl2 = 0, sl3 = 0;
+    if (v0) { bi0 = __umulhi(key0, e_first - lo); sl0 = atomicAdd(&bkt[bi0], 1u); }
+    if (v1) { bi1 = (s1 - lo) + __umulhi(key1, e1 - s1); sl1 = atomicAdd(&bkt[bi1], 1u); }
+    if (v2) { bi2 = (s2 - lo) + __umulhi(key2, e2 - s2); sl2 = atomicAdd(&bkt[bi2], 1u); }
+    if (v3) { bi3 = (s_last - lo) + __umulhi(key3, hi - s_last); sl3 = atomicAdd(&bkt[bi3], 1u); }
+    __syncthreads();
+    // exclusive prefix sum of the m counters, four per lane
+    uint32_t v[4], tsum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = bkt[4 * t + k]; tsum += v[k]; }     // (counters behind m are zero)
+    const uint32_t incl = wave_inclusive_scan(tsum);
+    if (lane_id() == WAVE - 1) wsum[wave_id()] = incl;
+    __syncthreads();
+    uint32_t run = incl - tsum;
+#pragma unroll
+    for (int w = 0; w < BS / WAVE; ++w) if (w < int(wave_id())) run += wsum[w];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { bkt[4 * t + k] = run; run += v[k]; }
+    __syncthreads();
+    if (v0) lds[bkt[bi0] + sl0] = key0;
+    if (v1) lds[bkt[bi1] + sl1] = key1;
+    if (v2) lds[bkt[bi2] + sl2] = key2;
+    if (v3) lds[bkt[bi3] + sl3] = key3;
+    __syncthreads();
+    auto place = [&](bool valid, uint32_t bi, KEY mine, uint32_t id) {
+      if (!valid) return;
+      const uint32_t b0 = bkt[bi], b1 = bi + 1 < m ? bkt[bi + 1] : m;
+      uint32_t rank = b0;
+      for (uint32_t q = b0; q < b1; ++q) rank += lds[q] < mine;
+      const size_t pos = size_t(lo) + rank;
+      if (pos >= P0 && pos <= P0 + OWN) ids[pos - P0] = id;
+    };
+    place(v0, bi0, key0, id0); place(v1, bi1, key1, id1); place(v2, bi2, key2, id2); place(v3, bi3, key3, id3);
+  } else {
+    // counting in memory, every entry of the touched cells in turn
+    for (size_t q = size_t(lo) + t; q < size_t(hi); q += BS) {
+      const uint32_t id = in[q], c = sorted_ijk[q], s = cell_start[c], e = cell_start[c + 1];
+      const KEY mine = shuffle_un(id, r.s1, r.s2);
+      uint32_t rank = 0;
+      for (uint32_t j = s; j < e; ++j) rank += shuffle_un(in[j], r.s1, r.s2) < mine;
+      const size_t pos = size_t(s) + rank;
+      if (pos >= P0 && pos <= P0 + OWN) ids[pos - P0] = id;
+    }
+  }
+  __syncthreads();
+  if (!pair_lane) return;
+  const uint32_t i0 = ids[2 * t], i1 = ids[2 * t + 1], i2 = has2 ? ids[2 * t + 2] : 0u;
+  coal_pair<T, false>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,
+                      (T *)nullptr, ijk_mark);
 }
 // weighted_summator, coal.ipp:57-97,458-480 (only with more than one kappa in the run)
 template <class T>

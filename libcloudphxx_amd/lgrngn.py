@@ -122,6 +122,7 @@ class dbg(enum.IntFlag):
     COND_NO_FUSED_SUBSTEPS = 1 << 27
     VTERM_INVALID_OWN_PASS = 1 << 28
     RLX_GLOBAL_ATOMICS = 1 << 29
+    NO_RANK_IN_COAL = 1 << 30
 
 
 class cond_kernel(enum.IntEnum):
