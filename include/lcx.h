@@ -159,6 +159,7 @@ typedef struct {
                          * The lean solver's folded kernel (k_cond_lean_fold): > 0 = slots of its LDS stage in use (at most 128; a test makes it
                          * small so that unconverged droplets stay in their own lanes) */
   int dbg_pack_delay_us;/* multi-device tests: slabs with an odd first plane send their messages so many microseconds late */
+  unsigned dbg_flags2;  /* LCX_DBG2_* bits below (enum lcx_dbg is full) */
   /* box in which the aerosol source creates super-droplets (opts_init.hpp: src_x0 .. src_z1, default 0; src_type above:
    * 0 off, 1 simple, 2 matching, ccn_source.hpp).  src_x0 == src_x1 == 0 switches the source of this domain off. */
   double src_x0, src_y0, src_z0, src_x1, src_y1, src_z1;
@@ -226,6 +227,14 @@ enum lcx_dbg {
                                         * inside the coalescence kernel that consumes it (k_coal_ranked: the same bits; "raw_coal_ranked") */
   LCX_DBG_COND_TOMS_TWO_PASS = 1 << 15 /* cond_solver = 1 through round 2's kernels (k_cond_fast_fold + k_cond_fast over the sorted order, iteration budget and
                                         * straggler launch) instead of the storage-order kernel with TOMS748 in it */
+};
+
+/* bit 31 of dbg_flags (an enum constant has to fit an int) */
+#define LCX_DBG_NO_COAL_SKIP (1u << 31) /* coalescence that ranks for itself (k_coal_ranked) without the per-cell bound on the pairs' collision probability:
+                                         * every pair's attributes are gathered, as in round 7 (the same bits; "raw_coal_skip") */
+enum lcx_dbg2 {
+  LCX_DBG2_COAL_SKIP_COUNT = 1 << 0    /* measurement / tests: k_coal_ranked counts the pairs it examines and the pairs it skips (two atomics per wave;
+                                        * lcx_get_state_u64 "raw_coal_skip" = { launches of the last lcx_step_async that used a bound, skipped, examined }) */
 };
 
 /* lcx_get_state_u64("raw_mode") = { strict_fp, cond_solver, the kernel of the last condensation launch (below; 0: none yet), dbg_flags } as

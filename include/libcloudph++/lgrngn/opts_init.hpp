@@ -67,6 +67,7 @@ namespace libcloudphxx { namespace lgrngn {
     // slab: leaving SDs are listed for lcx_migrate_pack, 3 open wall)
     int n_x_bfr = 0, bcond_lft = 0, bcond_rgt = 0;
     unsigned dbg_flags = 0;    // test / measurement switches (lcx.h, enum lcx_dbg): all off in production
+    unsigned dbg_flags2 = 0;   // ... continued (lcx.h, enum lcx_dbg2)
     int reorder_every = 0;     // storage re-ordering into the cell-sorted order: every N steps and with every compaction (0: N = 64), -1 never (lcx.h)
     bool stream_ordered = false; // device arrays: step_sync returns once its work is queued on the object's stream (lcx.h)
   };

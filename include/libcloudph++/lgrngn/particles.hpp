@@ -158,6 +158,7 @@ namespace libcloudphxx { namespace lgrngn {
       c.src_type = int(o.src_type); c.th_dry = o.th_dry; c.const_p = o.const_p; c.diag_incloud_time = o.diag_incloud_time;
       c.n_x_tot = n_x_tot; c.strict_fp = o.strict_fp; c.cond_solver = o.cond_solver; c.reorder_every = o.reorder_every; c.stream_ordered = o.stream_ordered;
       c.dbg_flags = o.dbg_flags;
+      c.dbg_flags2 = o.dbg_flags2;
       c.n_x_bfr = o.n_x_bfr; c.bcond_lft = o.bcond_lft; c.bcond_rgt = o.bcond_rgt;
       c.chem_rho = o.chem_rho;
       c.src_x0 = o.src_x0; c.src_y0 = o.src_y0; c.src_z0 = o.src_z0; c.src_x1 = o.src_x1; c.src_y1 = o.src_y1; c.src_z1 = o.src_z1;

@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -286,6 +287,7 @@ struct Particles : IParticles {
   bool in_init = false;
   long long seed_now() const { return in_init && o.rng_seed_init_switch ? o.rng_seed_init : o.rng_seed; }
   bool replay_used = false;   // a parity run: storage stays in the reference's id order (see opts_init.reorder_every)
+  bool dbg2(unsigned f) const { return (o.dbg_flags2 & f) != 0; }
   bool dbg(unsigned f) const { return (o.dbg_flags & f) != 0; }      // test / measurement switches (include/lcx.h, lcx_dbg): read from the options, never from the environment
   bool no_cond_pre = dbg(LCX_DBG_NO_COND_PRE);   // test switch: evaluate the per-cell set-up per droplet instead
   uint64_t cells_version = 0;   // order_cells: the list of cells above CELLRANK_MAX is remembered per cell_start
@@ -352,6 +354,32 @@ struct Particles : IParticles {
   double puddle[LCX_OUT_COUNT];
   bool count_mom_valid_all = true;
   double kernel_r_max = 0; int n_user_params = 0;
+  // ---- coal_pair's probability bound (k_coal_ranked<.., SKIP>, round 8) ----
+  DevBuf<uint32_t> coal_cmax;                // per cell: the bits of the largest rw2 and vt that the last hskpng_vterm(false, true) wrote
+  DevBuf<n_t> coal_n_max;                    // the largest multiplicity in storage ...
+  bool n_max_stale = true;                   // ... to be recomputed: something other than coalescence has written multiplicities (init, set_particles,
+                                             // a source, relaxation, recycling, immigrants) -- coalescence itself only lowers them
+  DevBuf<T> coal_emax; int n_emax = 0;       // the efficiency table's running maximum by kernel_index (init_kernel); 0: no bound for this kernel
+  DevBuf<unsigned long long> coal_skip_cnt;  // LCX_DBG2_COAL_SKIP_COUNT: {pairs skipped, pairs examined} of the last step_async
+  // the bound pays only where it skips: a sample of the launch's counters comes back to the host without a wait (a copy and an event, polled by
+  // the next step_async); below COAL_SKIP_MIN_SHARE^-1 of the pairs skipped, COAL_SKIP_PAUSE steps run without maxima and without bound, then
+  // one step probes again.  Results do not depend on it: a launch with the bound and one without give the same bits.
+  static constexpr int COAL_SKIP_PAUSE = 32; static constexpr unsigned long long COAL_SKIP_MIN_SHARE = 200;      // (0.5 %)
+  DevBuf<unsigned long long> coal_skip_sample; void *skip_pinned = nullptr; hipEvent_t ev_skip = nullptr;
+  bool skip_sample_pending = false; int skip_sample_n = 0, skip_pause = 0;
+  void poll_skip_sample()
+  {
+    if (!skip_sample_pending || hipEventQuery(ev_skip) != hipSuccess) return;
+    skip_sample_pending = false;
+    const unsigned long long *h = static_cast<const unsigned long long *>(skip_pinned);
+    unsigned long long skipped = 0, examined = 0;
+    for (int i = 0; i < skip_sample_n; i += 2) { skipped += h[i]; examined += h[i + 1]; }
+    if (examined && skipped * COAL_SKIP_MIN_SHARE < examined) skip_pause = COAL_SKIP_PAUSE;
+  }
+  bool coal_bound_armed = false;             // step_async's own hskpng_vterm has just left the maxima: the FIRST coalescence substep may use them
+  int last_coal_skip = 0;                    // ("raw_coal_skip": the coalescence launches of the last step_async that used a bound)
+  unsigned long long coal_bound_unused = 0;  // ("raw_coal_bound_unused": step_asyncs of this object whose velocity pass collected maxima that no launch used --
+                                             // coal_skip_wanted() said yes ahead of the pass and coal() then took another kernel: cost without a skip, made visible)
   double log_rd_min = 0, log_rd_max = 0, multiplier = 0;
   T eps_tol;
   vt_cfg vtc;
@@ -476,6 +504,8 @@ struct Particles : IParticles {
     for (hipEvent_t e : prof_pool) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
     if (pinned) (void)hipHostFree(pinned);
+    if (skip_pinned) (void)hipHostFree(skip_pinned);
+    if (ev_skip) (void)hipEventDestroy(ev_skip);
     // (the copy stream reads the staging areas: it is drained before they are freed)
     if (st_copy) { (void)hipStreamSynchronize(st_copy); (void)hipStreamDestroy(st_copy); }
     for (HostStage *h : {&hstage_in, &hstage_out}) if (h->p) (void)hipHostFree(h->p);
@@ -1040,10 +1070,12 @@ struct Particles : IParticles {
   }
   void hskpng_sort() { finish_deferred_sort(); if (!sorted) hskpng_sort_helper(false); }
   void hskpng_count() { hskpng_sort(); }
-  void hskpng_vterm(bool only_invalid)
+  // cell_max (step_async alone, ahead of a coalescence that ranks for itself): the all-droplets pass also leaves every cell's largest rw2
+  // and vt for coal_pair's bound (k_vterm_b77<.., CELLMAX>).  Returns whether it has: the other formulas' pass (k_vterm) produces none.
+  bool hskpng_vterm(bool only_invalid, bool cell_max = false)
   {
     Range r(this, only_invalid ? "hskpng_vterm_invalid" : "hskpng_vterm_all");
-    if (!nphys) return;
+    if (!nphys) return false;
     if (vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST) {
       if (!vtpre_valid) {
         vt_pre.alloc(ncell);
@@ -1051,13 +1083,22 @@ struct Particles : IParticles {
         vtpre_valid = true;
       }
       const dim3 gv(nblk(nphys, 2 * BS * VT_CHUNKS));                   // VT_CHUNKS pairs of super-droplets per lane
-      auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p); };
+      auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, (uint32_t *)nullptr); };
       const bool table = vtc.formula == LCX_VT_BEARD77FAST;
+      if (cell_max && !only_invalid) {
+        coal_cmax.alloc(2 * ncell);
+        HIPCHK(hipMemsetAsync(coal_cmax.p, 0, 2 * ncell * sizeof(uint32_t), st));
+        auto launch_max = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, 0, vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, coal_cmax.p); };
+        if (o.strict_fp) { if (table) launch_max(k_vterm_b77<T, false, true, true>); else launch_max(k_vterm_b77<T, false, false, true>); }
+        else             { if (table) launch_max(k_vterm_b77<T, true, true, true>); else launch_max(k_vterm_b77<T, true, false, true>); }
+        return true;
+      }
       if (o.strict_fp) { if (table) launch(k_vterm_b77<T, false, true>); else launch(k_vterm_b77<T, false, false>); }
       else             { if (table) launch(k_vterm_b77<T, true, true>); else launch(k_vterm_b77<T, true, false>); }
-      return;
+      return false;
     }
     hipLaunchKernelGGL(k_vterm<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, Tk.p, p.p, rhod.p, eta.p, vt_0.p, A.vt.p);
+    return false;
   }
   // cells per workgroup of the LDS-staged per-cell walks: as many as fit the staging buffer at the mean occupancy (+25 %)
   int cf_cells() const
@@ -1096,6 +1137,7 @@ struct Particles : IParticles {
   void rcyc()
   {
     if (!nphys) return;
+    n_max_stale = true;
     const size_t N = nphys;
     rc_stat.alloc_zero(4, st); rc_max.alloc_zero(1, st);
     hipLaunchKernelGGL(k_rcyc_stat, dim3(nblk(N)), dim3(BS), 0, st, A.n.p, N, rc_stat.p, rc_max.p);
@@ -1649,11 +1691,35 @@ struct Particles : IParticles {
   bool coal_will_rank() const { return coal_ranks_config() && owed_order_rankable() && last_async_coal; }
   int last_coal_ranked = 0;                  // ("raw_coal_ranked": the coalescence launches of the last step_async that ranked for themselves)
   int last_coal_kernel = 0;                  // (the k_coal variant of the last launch, "raw_coal_kernel": 0 generic, 1 Onishi, 2 production)
+  // step_async: does this step's coalescence go through k_coal_ranked with a bound (the conditions of its launch in coal(), as far as they are
+  // known ahead of the velocity pass -- where coal() then takes another kernel after all, the maxima were collected for nothing)
+  // the two conditions of coal() below, shared with step_async's look ahead so that they cannot drift apart: the cells are unchanged since the
+  // last sort and no shuffle was made ahead (coal() then owes the shuffle as well) ...
+  bool coal_owes_unshuffled_cells() const { return sorted && !(sorted_shuffled && shuffle_fresh) && coal_ranks_config() && cells_rankable(); }
+  // ... and: the order is owed, so the first substep's launch ranks for itself
+  bool coal_ranks_owed_order() const { return rank_owed && coal_ranks_config() && owed_order_rankable() && sorted && sorted_shuffled; }
+  bool coal_skip_wanted() const
+  {
+    // (a sort still deferred is finished inside coal() and changes what the two conditions see: no bound then.  Under lcx_set_profiling(1) the
+    // ranking is a kernel of its own and nothing is owed: no maxima are collected for the stage table's coalescence.)
+    return !dbg(LCX_DBG_NO_COAL_SKIP) && n_emax > 0 && nphys > 0 && (vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST) &&
+           !sort_deferred && (coal_ranks_owed_order() || coal_owes_unshuffled_cells());
+  }
+  void refresh_n_max()
+  {
+    if (!n_max_stale) return;
+    coal_n_max.alloc(1);
+    HIPCHK(hipMemsetAsync(coal_n_max.p, 0, sizeof(n_t), st));
+    if (nphys) hipLaunchKernelGGL(k_n_max, dim3(std::min(nblk(nphys), 2048u)), dim3(BS), 0, st, nphys, (const n_t *)A.n.p, coal_n_max.p);
+    n_max_stale = false;
+  }
   void coal(double dt_sub, bool turb_coal = false, bool first_substep = true)
   {
+    const bool bound_armed = coal_bound_armed && first_substep;      // (the maxima of step_async's own velocity pass: this call or none)
+    coal_bound_armed = false;
     if (!replay.empty()) ensure_compact();     // un[id] of a replayed CPU stream is indexed by the reference's (compact) ids
     finish_deferred_sort();
-    if (first_substep && sorted && !(sorted_shuffled && shuffle_fresh) && coal_ranks_config() && cells_rankable()) {
+    if (first_substep && coal_owes_unshuffled_cells()) {
       // cells unchanged since the last sort, no shuffle made ahead (the first step of a run, a step whose re-sort was not carried): the
       // shuffle that hskpng_sort_helper would launch is owed as well -- the salts drawn now, at their place in the generator's sequence
       deferred_shuffle = true; deferred_rs = rand_un(npart); last_shuffle_rs = deferred_rs;
@@ -1669,15 +1735,30 @@ struct Particles : IParticles {
     // The order this coalescence pairs up is still owed (hskpng_sort_helper has found it `fresh` and ranked nothing): the kernel that ranks
     // for itself takes the cells as the scatter left them.  The debt stays -- sorted_id in memory is in arrival order -- until somebody
     // reads the order (pay_rank) or the step's re-sort makes it void.
-    if (rank_owed && first_substep && coal_ranks_config() && owed_order_rankable() && sorted && sorted_shuffled && !rs.arr) {
+    if (first_substep && coal_ranks_owed_order() && !rs.arr) {
       coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
       const dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));
       last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
+      coal_skip_args<T> ska{};
+      if (bound_armed && !n_max_stale) {
+        const bool counted = dbg2(LCX_DBG2_COAL_SKIP_COUNT);
+        if (!counted) { coal_skip_sample.alloc(64); HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 64 * sizeof(unsigned long long), st)); }
+        ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p};
+        ++last_coal_skip;
+      }
       auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
-                           deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr);
+                           deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska);
       };
-      if (coal_marks_dead) launch(k_coal_ranked<T, true>); else launch(k_coal_ranked<T, false>);
+      if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true>); else launch(k_coal_ranked<T, false, true>); }
+      else if (coal_marks_dead) launch(k_coal_ranked<T, true>); else launch(k_coal_ranked<T, false>);
+      if (ska.cmax && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
+        if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 64 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
+        skip_sample_n = ska.cnt ? 2 : 64;
+        HIPCHK(hipMemcpyAsync(skip_pinned, ska.cnt ? ska.cnt : ska.sample, skip_sample_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(ev_skip, st));
+        skip_sample_pending = true;
+      }
       return;
     }
     const bool onishi = o.kernel == LCX_KERNEL_ONISHI_HALL || o.kernel == LCX_KERNEL_ONISHI_HALL_DAVIS_NO_WAALS;
@@ -2041,6 +2122,7 @@ struct Particles : IParticles {
   // void the histogram of a fused move, so a step that is short of room does not take the fused move, step_async)
   size_t src_make_room(size_t n_new)
   {
+    n_max_stale = true;                            // (an entry fires and appends n_new > 0 droplets; matching also raises old droplets' multiplicities)
     if (nphys + n_new > cap && !distmem()) {       // dead super-droplets not yet compacted away may be in the way
       lcx_opts_t od; lcx_opts_default(&od);
       post_copy(od, true);
@@ -2213,6 +2295,7 @@ struct Particles : IParticles {
     uint32_t n_new = 0;
     read_back(&n_new, rlx_total.p, 1);
     if (n_new == 0) return;
+    n_max_stale = true;
     Range r(this, "rlx_create");
     const size_t n_old = src_make_room(n_new);
     const u01_src<T> r_i = rand_u01(n_new), r_rd = rand_u01(n_new), r_j = n_dims == 3 ? rand_u01(n_new) : u01_src<T>{nullptr, 0, 0};
@@ -2244,6 +2327,22 @@ struct Particles : IParticles {
           throw lcx_error("libcloudph++: collision efficiency table of kernel " + std::to_string(o.kernel) + " not found or unreadable (" + tried +
                           "); set LCX_DATA_DIR to the directory that holds kernel_eff_*.f64");
         params.insert(params.end(), tab.begin(), tab.end());                             // user parameters first, then the efficiencies
+        // coal_pair's bound: emax[i] = the largest efficiency at any node that interpolated_efficiency can read while both radii lie in intervals
+        // whose lower node has kernel_index <= i.  The upper node of interval i is node i + 1 in either spacing (x0 + 1 below 100 um, x0 + 10 above,
+        // 99 + 1 = node 100), so these are the rows 0 ... i + 1 of the triangular table (row a: the pairs (a, j <= a)).  The radius clamp at
+        // r_max needs no entry: the kernel does not skip a cell within 11 um of the table's end.
+        size_t nn = size_t((std::sqrt(8. * double(tab.size()) + 1.) - 1.) / 2. + .5);
+        if (!onishi && nn >= 2 && nn * (nn + 1) / 2 == tab.size() && nn <= size_t(EMAX_CAP)) {
+          std::vector<T> em(nn);
+          double run = -std::numeric_limits<double>::infinity();
+          size_t row = 0;
+          for (size_t i = 0; i < nn; ++i) {
+            for (; row <= std::min(i + 1, nn - 1); ++row) for (size_t j = 0; j <= row; ++j) run = std::max(run, tab[row * (row + 1) / 2 + j]);
+            em[i] = T(run);
+            if (double(em[i]) < run) em[i] = std::nextafter(em[i], std::numeric_limits<T>::infinity());      // (fp32: rounded up)
+          }
+          if (run == run && run < 1e30) { coal_emax.alloc(nn); h2d(coal_emax.p, em.data(), nn * sizeof(T)); n_emax = int(nn); }
+        }
       }
     }
     std::vector<T> h(params.begin(), params.end());
@@ -2529,13 +2628,22 @@ struct Particles : IParticles {
     const bool rlx_now = opts.rlx && rlx_fires();
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
-    last_coal_ranked = 0;
+    last_coal_ranked = 0; last_coal_skip = 0; coal_bound_armed = false;
+    if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) coal_skip_cnt.alloc_zero(2, st);
     vt_fix_pending = false;                           // (a flag of one step_async: nothing of an earlier call is pending)
     last_async_coal = opts.coal != 0;
     coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
                                                        // substeps a used-up SD still takes part in the later ones and keeps its cell)
     hskpng_Tpr(opts.sedi || opts.coal || opts.cond);
-    if (opts.sedi || opts.coal || opts.cond) hskpng_vterm(false);
+    // (the velocity pass leaves the per-cell maxima of coal_pair's bound where the first coalescence substep, right behind it, will rank for itself:
+    // nothing in between writes rw2, vt, n or the cells)
+    poll_skip_sample();
+    const bool paused = opts.coal && skip_pause > 0;
+    if (paused) --skip_pause;
+    const bool want_bound = opts.coal && !paused && coal_skip_wanted();
+    if (want_bound) refresh_n_max();
+    if (opts.sedi || opts.coal || opts.cond) coal_bound_armed = hskpng_vterm(false, want_bound);
+    const bool bound_collected = coal_bound_armed;
     if (opts.coal) {
       for (int step = 0; step < sstp_coal; ++step) {
         coal(dt / sstp_coal, opts.turb_coal, step == 0);
@@ -2547,6 +2655,7 @@ struct Particles : IParticles {
         read_back(&flag, d_flag.p, 1);
         if (flag) { ++sstp_coal; HIPCHK(hipMemsetAsync(d_flag.p, 0, sizeof(int), st)); }
       }
+      if (bound_collected && last_coal_skip == 0) ++coal_bound_unused;
       release_replay_keep();
       hskpng_approximate_rc2_invalid();                                                  // particles_step.ipp:402-403
     }
@@ -2738,6 +2847,11 @@ struct Particles : IParticles {
       v = {(unsigned long long)(o.strict_fp ? 1 : 0), (unsigned long long)o.cond_solver, (unsigned long long)last_cond_kernel, (unsigned long long)o.dbg_flags};
     }
     else if (s == "raw_coal_ranked") v.assign(1, (unsigned long long)last_coal_ranked);
+    else if (s == "raw_coal_skip") {               // launches of the last step_async that used a bound; LCX_DBG2_COAL_SKIP_COUNT: + pairs skipped, pairs examined
+      v.assign(1, (unsigned long long)last_coal_skip);
+      if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) { if (coal_skip_cnt.p) { auto h = d2h(coal_skip_cnt.p, 2); v.insert(v.end(), h.begin(), h.end()); } else v.insert(v.end(), 2, 0ull); }
+    }
+    else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
       unsigned long long c = 0;
@@ -2841,6 +2955,7 @@ struct Particles : IParticles {
       h2d(b.p, h.data(), n * sizeof(T));
     };
     h2d(A.n.p, mult, n * sizeof(n_t));
+    n_max_stale = true;
     up(A.rd3, rd3_); up(A.rw2, rw2_); up(A.kpa, kpa_); up(A.vt, vt_); up(A.x, x_); up(A.y, y_); up(A.z, z_);
     if (n) HIPCHK(hipMemsetAsync(ijk.p, 0, n * sizeof(uint32_t), st));     // every SD is in the order again, n == 0 included
     hskpng_ijk();
@@ -2857,6 +2972,7 @@ struct Particles : IParticles {
   {
     const std::string s(name);
     coal_marks_dead = false; zero_n_unmarked = true;                   // (single stages: nothing is fused)
+    coal_bound_armed = false;                                          // (... and no stage leaves a bound for another)
     if (s == "hskpng_Tpr") hskpng_Tpr();
     else if (s == "hskpng_mfp") hskpng_mfp();
     else if (s == "hskpng_ijk") hskpng_ijk();
@@ -2865,7 +2981,7 @@ struct Particles : IParticles {
     else if (s == "hskpng_count") hskpng_count();
     else if (s == "hskpng_vterm_all") hskpng_vterm(false);
     else if (s == "hskpng_vterm_invalid") hskpng_vterm(true);
-    else if (s == "coal") { adjust_timesteps(opts ? opts->dt : -1); coal(dt / sstp_coal, opts && opts->turb_coal); }
+    else if (s == "coal") { last_coal_skip = 0; adjust_timesteps(opts ? opts->dt : -1); coal(dt / sstp_coal, opts && opts->turb_coal); }
     else if (s == "adve") move(true, false, false, false);
     else if (s == "sedi") { adjust_timesteps(opts ? opts->dt : -1); move(false, true, false, false); }
     else if (s == "bcnd") move(false, false, false, true);
@@ -2906,6 +3022,7 @@ struct Particles : IParticles {
   void migrate_unpack(const void *buf, size_t cnt) override
   {
     if (!cnt) return;
+    n_max_stale = true;
     flag_emigrants();
     const size_t n_free = free_n[0] + free_n[1];
     size_t reuse = n_free > free_used ? std::min(cnt, n_free - free_used) : 0;

@@ -973,12 +973,48 @@ __device__ __forceinline__ bool vterm_b77_one(const vt_cfg &v, T r2, uint32_t c,
 // 2*BS-element chunk of its workgroup's range, so that every load instruction of a wave is one contiguous 1 KiB (rw2, vt) or 512 B (ijk).
 // C3: 1.05 ms with one element per lane, 0.82 ms with one pair, 1.31 ms with four CONSECUTIVE elements (strided lanes).
 constexpr int VT_CHUNKS = 2;
-template <class T, bool FAST, bool TABLE>
+// Round 8, CELLMAX (the all-droplets pass ahead of a coalescence that ranks for itself, lcx_core.hip coal_skip_wanted; off everywhere else): the
+// pass also leaves, per cell, the largest wet radius squared and the largest velocity among the droplets it writes, each as the bits of a float
+// rounded UP (positive floats order as unsigned integers) in cmax[2 c] and cmax[2 c + 1], cleared by the host -- what coal_pair's bound on a
+// pair's collision probability is made of.  A living droplet that the pass does not evaluate, or a velocity that is not >= 0, writes all-ones
+// bits (a NaN, and the largest unsigned): nothing is skipped in that cell.
+// Not a global atomic per droplet: every droplet offers its bits to a table of CM_SLOTS cells in the workgroup's LDS (open addressing on a
+// multiplicative hash of the cell, four probes, then straight to memory), with LDS atomics that return nothing but the claim of a slot; behind
+// a barrier each used slot leaves as two non-returning global atomics.  A workgroup's 1024 neighbours in storage lie in a few dozen cells.
+// (Measured and dropped: the lanes of a wave grouped by cell with ballots as in wave_hist_rank and reduced with DPP, one round per cell -- the
+// pass at 1.27 ms against 0.69 without the maxima, with or without its global atomics: a wave meets a dozen cells and more, and sixty
+// instructions per round double what the pass issues.)
+constexpr uint32_t CMAX_POISON = 0xFFFFFFFFu, CMAX_FLOOR = 0x00800000u;      // (FLT_MIN: a recorded maximum is never zero or subnormal)
+template <class T>
+__device__ __forceinline__ uint32_t float_bits_up(T x)                         // x > 0 (infinity included)
+{
+  const float f = float(x);
+  uint32_t b = __float_as_uint(f);
+  if (T(f) < x) ++b;                                                          // rounded down: the next float up
+  return b < CMAX_FLOOR ? CMAX_FLOOR : b;
+}
+constexpr int CM_BITS = 8, CM_SLOTS = 1 << CM_BITS;
+struct cellmax_lds { uint32_t key[CM_SLOTS], r[CM_SLOTS], v[CM_SLOTS]; };
+__device__ __forceinline__ void cellmax_offer(uint32_t *cmax, cellmax_lds &t, uint32_t c, uint32_t r, uint32_t v)
+{
+  uint32_t s = (c * 2654435761u) >> (32 - CM_BITS);
+#pragma unroll 1
+  for (int probe = 0; probe < 4; ++probe, s = (s + 1) & (CM_SLOTS - 1)) {
+    uint32_t prev = t.key[s];
+    if (prev == CMAX_POISON) prev = atomicCAS(&t.key[s], CMAX_POISON, c);
+    if (prev == CMAX_POISON || prev == c) { atomicMax(&t.r[s], r); atomicMax(&t.v[s], v); return; }
+  }
+  atomicMax(&cmax[2 * size_t(c)], r); atomicMax(&cmax[2 * size_t(c) + 1], v);
+}
+template <class T, bool FAST, bool TABLE, bool CELLMAX = false>
 __global__ void __launch_bounds__(BS)
-k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *ijk, const beard77_cell<T> *pre, const T *vt_0, T *vt)
+k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *ijk, const beard77_cell<T> *pre, const T *vt_0, T *vt, uint32_t *cmax = nullptr)
 {
   struct alignas(2 * sizeof(T)) pairT { T a, b; };
   struct alignas(8) pairU { uint32_t a, b; };
+  __shared__ cellmax_lds cm[1];                     // (unused, and dropped by the compiler, without CELLMAX)
+  static_assert(CM_SLOTS == BS, "a slot per thread");
+  if constexpr (CELLMAX) { cm[0].key[threadIdx.x] = CMAX_POISON; cm[0].r[threadIdx.x] = 0u; cm[0].v[threadIdx.x] = 0u; }
   const size_t base = size_t(blockIdx.x) * (2 * BS * VT_CHUNKS) + 2 * threadIdx.x;
   pairT r2[VT_CHUNKS], o[VT_CHUNKS]; pairU c[VT_CHUNKS];
 #pragma unroll
@@ -991,6 +1027,14 @@ k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *
     } else if (i < n) { r2[k] = pairT{rw2[i], T(0)}; c[k] = pairU{ijk[i], DEAD_CELL}; o[k] = pairT{only_invalid ? vt[i] : T(0), T(0)}; }
     else { r2[k] = pairT{T(0), T(0)}; c[k] = pairU{DEAD_CELL, DEAD_CELL}; o[k] = r2[k]; }
   }
+  // CELLMAX: the bits that each slot offers to its cell's maxima (a living droplet that is not evaluated: all ones)
+  // (CELLMAX stores the velocities BEHIND the maxima: a wave waits for its stores in flight before it may reuse their registers)
+  [[maybe_unused]] uint32_t mr[VT_CHUNKS][2], mv[VT_CHUNKS][2];
+  [[maybe_unused]] pairT res[VT_CHUNKS]; [[maybe_unused]] bool sa[VT_CHUNKS], sb[VT_CHUNKS];
+  if constexpr (CELLMAX) {
+#pragma unroll
+    for (int k = 0; k < VT_CHUNKS; ++k) { mr[k][0] = mr[k][1] = mv[k][0] = mv[k][1] = CMAX_POISON; sa[k] = sb[k] = false; }
+  }
 #pragma unroll
   for (int k = 0; k < VT_CHUNKS; ++k) {
     const size_t i = base + size_t(k) * 2 * BS;
@@ -998,10 +1042,51 @@ k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *
     T va = o[k].a, vb = o[k].b;
     const bool wa = !(only_invalid && !(va == T(-1))) && vterm_b77_one<T, FAST, TABLE>(v, r2[k].a, c[k].a, pre, vt_0, va);
     const bool wb = i + 1 < n && !(only_invalid && !(vb == T(-1))) && vterm_b77_one<T, FAST, TABLE>(v, r2[k].b, c[k].b, pre, vt_0, vb);
-    if (wa && wb) *reinterpret_cast<pairT *>(vt + i) = pairT{va, vb};
-    else if (wa) vt[i] = va;
-    else if (wb) vt[i + 1] = vb;
+    if constexpr (!CELLMAX) {
+      if (wa && wb) *reinterpret_cast<pairT *>(vt + i) = pairT{va, vb};
+      else if (wa) vt[i] = va;
+      else if (wb) vt[i + 1] = vb;
+    } else {
+      res[k] = pairT{va, vb}; sa[k] = wa; sb[k] = wb;
+      if (wa) { mr[k][0] = float_bits_up(r2[k].a); mv[k][0] = va > T(0) ? float_bits_up(va) : va == T(0) ? CMAX_FLOOR : CMAX_POISON; }
+      if (wb) { mr[k][1] = float_bits_up(r2[k].b); mv[k][1] = vb > T(0) ? float_bits_up(vb) : vb == T(0) ? CMAX_FLOOR : CMAX_POISON; }
+    }
   }
+  if constexpr (CELLMAX) {                             // (behind the loop: every thread of the workgroup is here; slots past n carry DEAD_CELL)
+    __syncthreads();                                   // (the table is cleared)
+#pragma unroll
+    for (int k = 0; k < VT_CHUNKS; ++k) {
+      const bool la = c[k].a != DEAD_CELL, lb = c[k].b != DEAD_CELL;
+      if (la && lb && c[k].a == c[k].b)                // (neighbours in storage, mostly of one cell: one offer)
+        cellmax_offer(cmax, cm[0], c[k].a, mr[k][0] > mr[k][1] ? mr[k][0] : mr[k][1], mv[k][0] > mv[k][1] ? mv[k][0] : mv[k][1]);
+      else {
+        if (la) cellmax_offer(cmax, cm[0], c[k].a, mr[k][0], mv[k][0]);
+        if (lb) cellmax_offer(cmax, cm[0], c[k].b, mr[k][1], mv[k][1]);
+      }
+    }
+    __syncthreads();
+    {
+      const uint32_t cell = cm[0].key[threadIdx.x];
+      if (cell != CMAX_POISON) { atomicMax(&cmax[2 * size_t(cell)], cm[0].r[threadIdx.x]); atomicMax(&cmax[2 * size_t(cell) + 1], cm[0].v[threadIdx.x]); }
+    }
+#pragma unroll
+    for (int k = 0; k < VT_CHUNKS; ++k) {
+      const size_t i = base + size_t(k) * 2 * BS;
+      if (sa[k] && sb[k]) *reinterpret_cast<pairT *>(vt + i) = res[k];
+      else if (sa[k]) vt[i] = res[k].a;
+      else if (sb[k]) vt[i + 1] = res[k].b;
+    }
+  }
+}
+// the largest multiplicity in storage (the third factor of coal_pair's bound; coalescence only lowers multiplicities, so the host computes it
+// only after something else has written them)
+__global__ void __launch_bounds__(BS) k_n_max(size_t n, const n_t *mult, n_t *out)
+{
+  n_t m = 0;
+  for (size_t i = gid(); i < n; i += size_t(gridDim.x) * BS) { const n_t x = mult[i]; m = x > m ? x : m; }
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) { const n_t x = __shfl_xor(m, d); m = x > m ? x : m; }
+  if (lane_id() == 0 && m) atomicMax(out, m);
 }
 template <class T>
 __global__ void k_vterm(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *ijk, const T *Tk, const T *p,
@@ -2437,22 +2522,51 @@ template <class T> struct u01_src { const T *arr; uint64_t call, seed; };
 // gathers are slower than the walk's independent lanes.)
 // the pair that the lane looking at position p0 owns, given the cells (c0, c1, c2) and ids (i0, i1, i2) of the positions p0, p0 + 1, p0 + 2 and
 // the CSR bounds of the first two cells: the body of k_coal, shared with the kernel that ranks the cells for itself (k_coal_ranked)
+// Round 8, the SKIP of k_coal_ranked (sk != nullptr; nullptr everywhere else, which then compiles to the code it was): a pair whose random
+// number u is at or above an upper bound on its collision probability cannot collide, and is left before any of its attributes is gathered
+// (48 B per pair, and in a cloud without drizzle no pair in ten thousand collides).  The bound is per cell,
+//     bound = dt / dv * scl * n_max * pi * 4 * rw2_max * vt_max * E_max * (1 + 2^-10),
+// of what the all-droplets velocity pass just ahead has left (k_vterm_b77<.., CELLMAX>: the cell's largest rw2 and vt as floats rounded up),
+// the largest multiplicity in storage and the largest tabulated efficiency that droplets no larger than the cell's largest can read.
+// prob <= bound, factor by factor of prob = dt / dv * scl * E(ra, rb) * pi * max(na, nb) * |vta - vtb| * (ra + rb)^2:
+//   - max(na, nb) <= n_max: coalescence only lowers multiplicities, and the host recomputes n_max after anything else that writes them;
+//   - every velocity of the cell is >= 0 (the pass writes all-ones bits for a cell where one is not), so |vta - vtb| <= max(vta, vtb) <= vt_max;
+//   - rw2a + rw2b + 2 sqrt(rw2a rw2b) = (ra + rb)^2 <= 4 rw2_max;
+//   - interpolated_efficiency is a convex combination (weights >= 0 that sum to one) of the four table nodes around (ra, rb): at most the
+//     largest node that radii up to the cell's largest can reach, emax[] (lcx_core.hip init_kernel), looked up at a radius inflated by 2^-10
+//     so that no rounding of a droplet's own square root and scaling puts it in a higher interval than the cell's; a cell within 11 um of
+//     the table's end is not skipped;
+//   - every factor is rounded up or exact, and the products on both sides are a dozen operations of relative error <= 2^-23 each (fp32; 2 ulp
+//     for the fast divisions): 2^-10 covers them in every arithmetic the kernel is built for.  A bound that would underflow is raised to 1e-30.
+// A poisoned cell, an infinite maximum or any NaN leaves `bound` NaN, and `bound < 1 && u >= bound` is then false: the full path runs.
+// Skipping changes nothing: with bound < 1, n_t(prob) = 0 and u < prob is false on the full path as well, which then returns having written
+// nothing (col == nullptr in the ranked kernel).
+template <class T> struct coal_skip_args {       // what the kernel is handed (cmax == nullptr: no skip)
+  const uint32_t *cmax; const n_t *n_max; const T *emax; int n_emax;
+  unsigned long long *cnt;                       // LCX_DBG2_COAL_SKIP_COUNT only: {pairs skipped, pairs examined}, one atomic each per wave
+  unsigned long long *sample;                    // else: 32 such pairs of counters, fed by every 64th workgroup -- what the host decides from whether the
+                                                 // bound is worth its maxima (lcx_core.hip poll_skip_sample: a drizzle box at dt = 1 skips 0.2 % of its pairs)
+};
+template <class T> struct coal_skip {            // what a lane has fetched of it ahead of the ranking, for the cells of its positions p0 and p0 + 1
+  uint32_t r0, v0, r1, v1; T dv0, dv1, n_max, r_max; const T *emax; int n_emax; unsigned long long *cnt;
+};
 template <class T, bool ONISHI>
 __device__ __forceinline__ void
 coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t i0, const uint32_t i1, const uint32_t i2,
           const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1,
           n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
-          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
+          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_skip<T> *sk = nullptr)
 {
   size_t p = p0;
   uint32_t ca = c0, off = off0, end = end0, a = i0, b = i1;
+  bool second = false;                                 // (the pair's cell is c1, not c0)
   {
     const bool even0 = ((uint32_t(p) - off) & 1u) == 0;
     if (!(even0 && c1 == ca)) {
       if (even0 && col) col[p] = T(0);                 // last SD of a cell with an odd count: no partner
       p = p0 + 1;
       if (!has2) return;
-      if (c1 != ca) { ca = c1; off = off1; end = end1; }
+      if (c1 != ca) { ca = c1; off = off1; end = end1; second = true; }
       if ((uint32_t(p) - off) & 1u) return;            // odd offset: this SD is the b of the previous lane's pair
       if (c2 != ca) { if (col) col[p] = T(0); return; }
       a = i1; b = i2;
@@ -2461,13 +2575,33 @@ coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1
   const uint32_t cnt = end - off;
   const n_t nn = cnt;
   const T scl = nn > 1 ? (T(nn * (nn - 1)) / 2) / (nn / 2) : T(0);           // scale_factor, coal.ipp:99-107
+  T u_pre = T(0), dvc_pre = T(0);
+  if (sk) {
+    const T rm = T(__uint_as_float(second ? sk->r1 : sk->r0)), vm = T(__uint_as_float(second ? sk->v1 : sk->v0));
+    dvc_pre = second ? sk->dv1 : sk->dv0;
+    T bound = T(__uint_as_float(CMAX_POISON));                                 // NaN
+    const T r_um = sqrt(rm) * T(1e6) * T(1 + 1. / 1024);
+    if (r_um < sk->r_max - T(11) && vm < T(3e38)) {                            // (false for a NaN)
+      const n_t x0 = r_um >= T(100) ? n_t(floor(r_um / 10) * 10) : n_t(floor(r_um));
+      const int ie = kernel_index(x0);
+      bound = dt / dvc_pre * scl * sk->n_max * T(cst<T>::pi * 4) * rm * vm * sk->emax[ie < sk->n_emax ? ie : sk->n_emax - 1] * T(1 + 1. / 1024);
+      if (bound < T(1e-30)) bound = T(1e-30);
+    }
+    u_pre = philox::u01<T>(p, rs.call, rs.seed);
+    const bool skip = bound < T(1) && u_pre >= bound;
+    if (sk->cnt) {
+      const unsigned long long here = __ballot(1), skipped = __ballot(skip);
+      if (int(lane_id()) == __ffsll((long long)here) - 1) { atomicAdd(sk->cnt, (unsigned long long)__popcll(skipped)); atomicAdd(sk->cnt + 1, (unsigned long long)__popcll(here)); }
+    }
+    if (skip) return;
+  }
   n_t na = n[a], nb = n[b];
-  T rw2a = rw2[a], rw2b = rw2[b], vta = vt[a], vtb = vt[b], dvc = dv[ca];
+  T rw2a = rw2[a], rw2b = rw2[b], vta = vt[a], vtb = vt[b], dvc = sk ? dvc_pre : dv[ca];
   asm volatile("" : "+v"(rw2a), "+v"(rw2b), "+v"(vta), "+v"(vtb), "+v"(dvc), "+v"(na), "+v"(nb));   // (one batch, not a chain)
   const T prob = dt / dvc * scl * kernel_calc<T, ONISHI>(kc, na, nb, rw2a, rw2b, vta, vtb, ca);
   n_t col_no = n_t(prob);
   if (pure_const_multi && col_no >= 1) *increase_sstp_coal = 1;
-  const T u = rs.arr ? rs.arr[p] : philox::u01<T>(p, rs.call, rs.seed);
+  const T u = sk ? u_pre : rs.arr ? rs.arr[p] : philox::u01<T>(p, rs.call, rs.seed);
   if (u < prob - col_no) ++col_no;
   if (col_no == 0) { if (col) { col[p] = T(0); col[p + 1] = T(0); } return; }
   if (na >= nb) {                                                            // collide<>, coal.ipp:110-143
@@ -2528,10 +2662,13 @@ k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, con
 // The barriers all sit AHEAD of the attribute gathers (see the LDS form that lost, above k_coal: workgroups waiting behind their gathers).
 constexpr int COAL_RANKED_POS = 2 * BS;
 // MARK: used-up super-droplets are marked in ijk (the step ends in the fused move), as in k_coal<T, false, true>
-template <class T, bool MARK>
+// SKIP: coal_pair's probability bound (above coal_pair); the table of efficiency maxima is copied to LDS ahead of the ranking's first barrier and the
+// per-cell maxima are fetched with the cells' bounds, so that behind the ranking a lane has one LDS read and arithmetic ahead of its gathers
+constexpr int EMAX_CAP = 256;
+template <class T, bool MARK, bool SKIP = false>
 __global__ void __launch_bounds__(BS)
 k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
-              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark)
+              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {})
 {
   using KEY = uint32_t;
   constexpr int CAP = 4 * BS, OWN = COAL_RANKED_POS;
@@ -2541,6 +2678,7 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   __shared__ uint32_t ids[OWN + 4];        // the ranked ids of the positions [P0, P0 + OWN]
   __shared__ uint32_t bounds[4];
   __shared__ uint32_t wsum[BS / WAVE];
+  __shared__ T emax_l[SKIP ? EMAX_CAP : 1];
   kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
   if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
   const size_t P0 = size_t(blockIdx.x) * OWN;
@@ -2563,6 +2701,20 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if (in2) { const uint32_t c = sorted_ijk[q2]; id2 = in[q2]; s2 = cell_start[c]; e2 = cell_start[c + 1]; }
   if (t == WAVE) { const uint32_t c = sorted_ijk[last]; bounds[1] = cell_start[c + 1]; bounds[3] = cell_start[c]; }   // (a wave that does not also hold lane 0)
   if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
+  [[maybe_unused]] coal_skip<T> sk;
+  if constexpr (SKIP) {
+    struct alignas(8) pairU { uint32_t a, b; };
+    pairU m0{CMAX_POISON, CMAX_POISON}, m1{CMAX_POISON, CMAX_POISON};
+    sk.dv0 = sk.dv1 = T(1);
+    if (pair_lane) {
+      m0 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c0)); m1 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c1));
+      sk.dv0 = dv[c0]; sk.dv1 = dv[c1];
+    }
+    sk.r0 = m0.a; sk.v0 = m0.b; sk.r1 = m1.a; sk.v1 = m1.b;
+    sk.n_max = T(*ska.n_max); sk.r_max = kc.r_max; sk.emax = emax_l; sk.n_emax = ska.n_emax;
+    sk.cnt = ska.cnt ? ska.cnt : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
+    if (int(t) < ska.n_emax) emax_l[t] = ska.emax[t];           // (n_emax <= EMAX_CAP = BS: the host launches this form only then)
+  }
 #pragma unroll
   for (int k = 0; k < CAP / BS; ++k) bkt[t + k * BS] = 0u;
   const KEY key0 = shuffle_un(id0, r.s1, r.s2), key1 = shuffle_un(id1, r.s1, r.s2), key2 = shuffle_un(id2, r.s1, r.s2), key3 = shuffle_un(id3, r.s1, r.s2);
@@ -2621,7 +2773,7 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if (!pair_lane) return;
   const uint32_t i0 = ids[2 * t], i1 = ids[2 * t + 1], i2 = has2 ? ids[2 * t + 2] : 0u;
   coal_pair<T, false>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,
-                      (T *)nullptr, ijk_mark);
+                      (T *)nullptr, ijk_mark, SKIP ? &sk : (const coal_skip<T> *)nullptr);
 }
 // weighted_summator, coal.ipp:57-97,458-480 (only with more than one kappa in the run)
 template <class T>

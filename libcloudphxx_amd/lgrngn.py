@@ -123,6 +123,12 @@ class dbg(enum.IntFlag):
     VTERM_INVALID_OWN_PASS = 1 << 28
     RLX_GLOBAL_ATOMICS = 1 << 29
     NO_RANK_IN_COAL = 1 << 30
+    NO_COAL_SKIP = 1 << 31
+
+
+class dbg2(enum.IntFlag):
+    """opts_init.dbg_flags2 (include/lcx.h, enum lcx_dbg2)"""
+    COAL_SKIP_COUNT = 1 << 0
 
 
 class cond_kernel(enum.IntEnum):
@@ -202,7 +208,7 @@ class _opts_init_c(C.Structure):
         ("dry_sizes", C.POINTER(_dry_size_c)), ("n_dry_sizes", C.c_int),
         ("n_x_tot", C.c_int), ("n_x_bfr", C.c_int), ("bcond_lft", C.c_int), ("bcond_rgt", C.c_int),
         ("strict_fp", C.c_int), ("cond_solver", C.c_int), ("reorder_every", C.c_int), ("stream_ordered", C.c_int),
-        ("dbg_flags", C.c_uint), ("dbg_cond_budget", C.c_int), ("dbg_pack_delay_us", C.c_int),
+        ("dbg_flags", C.c_uint), ("dbg_cond_budget", C.c_int), ("dbg_pack_delay_us", C.c_int), ("dbg_flags2", C.c_uint),
         ("src_x0", C.c_double), ("src_y0", C.c_double), ("src_z0", C.c_double),
         ("src_x1", C.c_double), ("src_y1", C.c_double), ("src_z1", C.c_double),
         ("rlx_bins", C.c_int), ("supstp_rlx", C.c_int), ("rlx_sd_per_bin", C.c_double), ("rlx_timescale", C.c_double),
@@ -349,6 +355,7 @@ class opts_init_t:
         self.dbg_flags = 0
         self.dbg_cond_budget = 0
         self.dbg_pack_delay_us = 0
+        self.dbg_flags2 = 0
 
     def _to_c(self, keep):
         c = _opts_init_c()

@@ -1,0 +1,135 @@
+"""CPU gate of the coalescence skip (k_coal_ranked<.., SKIP>, csrc/lcx_kernels.hpp coal_pair): how many candidate pairs, and how many
+128-byte lines of their attributes, are left to read once every pair with `bound < 1 and u >= bound` is skipped -- on the droplets of the
+OpenMP oracle on bench.py's fields, with k_geometric and interpolated_efficiency restated in numpy -- and the assertion that the bound is
+one: prob <= bound for every pair.
+
+    python3 tools/coal_skip_gate.py [--n 16] [--workload stratocumulus|coal-stress] [--dt 1] [--steps 5,50,200]
+
+Two bounds per cell: "table" takes the largest efficiency of the whole table, "radius" the largest one that radii up to the cell's largest
+can reach (what the kernel uses).  A line is 16 consecutive positions of the cell-sorted order, the granularity of the gathers' traffic.
+The pairing is the coalescence's: a random order inside each cell, pairs at even offsets.  For coal-stress the quantiles of the bound and
+the share of pairs that collide are printed as well (what tests/test_hip_coal_skip.py's time steps were chosen from).
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np                                            # noqa: E402
+import bench                                                  # noqa: E402
+import _harness as h                                          # noqa: E402
+from libcloudphxx_amd import lgrngn                           # noqa: E402
+
+MARGIN = 1 + 2. ** -10
+
+
+def load_table(kernel):
+    a = np.fromfile(os.path.join(ROOT, "libcloudphxx_amd", "data", "kernel_eff_%d.f64" % int(kernel)))
+    return a[0], a[2:2 + int(a[1])]
+
+
+def kernel_index(R):
+    return np.where(R <= 100, R, 100 + (R - 100) / 10.).astype(np.int64)
+
+
+def vec_index(i, j):
+    hi, lo = np.maximum(i, j), np.minimum(i, j)
+    return hi * (hi + 1) // 2 + lo
+
+
+def interpolated_efficiency(tab, r_max, r1, r2):
+    """kernel_interpolation.hpp:9-65 as csrc/lcx_kernels.hpp states it; radii in metres"""
+    r1, r2 = r1 * 1e6, r2 * 1e6
+    r1 = np.where(r1 >= r_max, r_max - 1e-6, r1)
+    r2 = np.where(r2 >= r_max, r_max - 1e-6, r2)
+    x0 = np.where(r1 >= 100, np.floor(r1 / 10) * 10, np.floor(r1)); dx = np.where(r1 >= 100, 10., 1.)
+    y0 = np.where(r2 >= 100, np.floor(r2 / 10) * 10, np.floor(r2)); dy = np.where(r2 >= 100, 10., 1.)
+    x1, y1 = x0 + dx, y0 + dy
+    i0, i1, j0, j1 = kernel_index(x0), kernel_index(x1), kernel_index(y0), kernel_index(y1)
+    w0, w1, w2, w3 = r1 - x0, x1 - r1, r2 - y0, y1 - r2
+    return (tab[vec_index(i0, j0)] * w1 * w3 + tab[vec_index(i1, j0)] * w0 * w3 + tab[vec_index(i0, j1)] * w1 * w2 + tab[vec_index(i1, j1)] * w0 * w2) / dx / dy
+
+
+def efficiency_maxima(tab):
+    """lcx_core.hip init_kernel: emax[i] = the largest node of the rows 0 ... i + 1 of the triangular table"""
+    nn = int(round((np.sqrt(8. * len(tab) + 1) - 1) / 2))
+    assert nn * (nn + 1) // 2 == len(tab)
+    rows = np.array([tab[a * (a + 1) // 2: a * (a + 1) // 2 + a + 1].max() for a in range(nn)])
+    run = np.maximum.accumulate(rows)
+    return np.array([run[min(i + 1, nn - 1)] for i in range(nn)])
+
+
+def float_up(x):
+    f = x.astype(np.float32)
+    return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float64)
+
+
+def gate(orc, oi, tab, r_max, emax, rng, label):
+    n, rw2, vt, ijk = orc.state_u64("n").astype(np.float64), orc.get_attr("rw2"), orc.state_real("vt"), orc.state_u64("ijk").astype(np.int64)
+    ncell = oi.nx * oi.ny * oi.nz
+    dv = oi.dx * oi.dy * oi.dz
+    order = np.lexsort((rng.random(len(n)), ijk))            # the cells in turn, a random order inside each
+    c = ijk[order]
+    start = np.searchsorted(c, np.arange(ncell + 1))
+    cnt = np.diff(start)
+    off = np.arange(len(c)) - start[c]
+    first = (off % 2 == 0) & (off + 1 < cnt[c])
+    pa, pb = np.nonzero(first)[0], np.nonzero(first)[0] + 1
+    a, b, cell = order[pa], order[pb], c[pa]
+    nn = cnt[cell].astype(np.float64)
+    scl = (nn * (nn - 1) / 2) / np.floor(nn / 2)
+    geom = np.pi * np.maximum(n[a], n[b]) * np.abs(vt[a] - vt[b]) * (rw2[a] + rw2[b] + 2 * np.sqrt(rw2[a] * rw2[b]))
+    prob = oi.dt / dv * scl * interpolated_efficiency(tab, r_max, np.sqrt(rw2[a]), np.sqrt(rw2[b])) * geom
+    u = rng.random(len(pa))
+    rw2_max, vt_max = np.zeros(ncell), np.zeros(ncell)
+    np.maximum.at(rw2_max, ijk, float_up(rw2)); np.maximum.at(vt_max, ijk, float_up(vt))
+    assert (vt >= 0).all()
+    r_um = np.sqrt(rw2_max) * 1e6 * MARGIN
+    x0 = np.where(r_um >= 100, np.floor(r_um / 10) * 10, np.floor(r_um))
+    e_radius = np.where(r_um < r_max - 11, emax[np.minimum(kernel_index(x0), len(emax) - 1)], np.nan)
+    base = oi.dt / dv * scl * n.max() * np.pi * 4 * rw2_max[cell] * vt_max[cell] * MARGIN
+    n_lines = (len(c) + 15) // 16
+    print("%s: %d pairs, largest pair probability %.3g, pairs that collide (u < prob) %.3g" % (label, len(pa), prob.max(), (u < prob).mean()))
+    for name, e in (("table", np.full(ncell, tab.max())), ("radius", e_radius)):
+        bound = base * e[cell]
+        ok = ~(prob > bound)
+        assert ok.all(), (name, int((~ok).sum()), float((prob / bound)[~ok].max()))
+        skip = (bound < 1) & (u >= bound)
+        assert not (skip & (u < prob)).any()
+        kept = ~skip
+        lines = np.unique(np.concatenate([pa[kept] // 16, pb[kept] // 16]))
+        q = np.nanpercentile(bound, [1, 10, 50, 99])
+        print("  %-6s bound: pairs kept %.5f, lines kept %.5f, skipped %.5f; bound quantiles 1 %% %.3g, 10 %% %.3g, median %.3g, 99 %% %.3g; cells with bound < 1: %.3f"
+              % (name, kept.mean(), len(lines) / n_lines, skip.mean(), q[0], q[1], q[2], q[3], (bound < 1).mean()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--workload", default="stratocumulus", choices=["stratocumulus", "coal-stress"])
+    ap.add_argument("--dt", type=float, default=1.)
+    ap.add_argument("--steps", default="5,50,200")
+    args = ap.parse_args()
+    at = sorted(int(s) for s in args.steps.split(","))
+    n = args.n
+    oi = bench.make_opts_init(n, n, n, 64, 40., 1, 1, 44, args.workload, args.dt)
+    r_max, tab = load_table(oi.kernel)
+    emax = efficiency_maxima(tab)
+    print("kernel %s: table maximum %.4g, maximum reachable up to 15 um %.4g" % (lgrngn.kernel_t(oi.kernel).name, tab.max(), emax[15]))
+    th, rv, rhod, Cx, Cy, Cz = bench.make_fields(n, n, n, 0, n, np, np.float64)
+    orc = h.oracle_omp_particles(oi)
+    orc.init(th, rv, rhod, Cx=Cx, Cy=Cy, Cz=Cz)
+    opts = lgrngn.opts_t()
+    rng = np.random.default_rng(7)
+    for step in range(1, at[-1] + 1):
+        orc.step_sync(opts, th, rv, rhod, Cx, Cy, Cz)
+        if step in at:                                       # what this step's coalescence will see: the droplets behind condensation, velocities fresh
+            orc.stage("hskpng_Tpr"); orc.stage("hskpng_vterm_all")
+            gate(orc, oi, tab, r_max, emax, rng, "step %d" % step)
+        orc.step_async(opts)
+
+
+if __name__ == "__main__":
+    main()
