@@ -15,6 +15,7 @@
 #include "backend.hpp"
 #include "../../lcx.h"
 #include "../../lcx_chem.h"
+#include "../../lcx_state.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -76,6 +77,10 @@ namespace libcloudphxx { namespace lgrngn {
     virtual std::map<common::output_t, real_t> diag_puddle() { assert(false); return std::map<common::output_t, real_t>(); }
     virtual std::vector<real_t> get_attr(const std::string &) { assert(false); return std::vector<real_t>(); }
     virtual real_t *outbuf() { assert(false); return nullptr; }
+    // checkpoint and restart (no reference counterpart; include/lcx_state.h): snapshot() after init() or step_async(), restore() on a fresh
+    // object made from the same opts_init IN THE PLACE OF init().  The caller keeps his own Eulerian fields and step counter.
+    virtual std::vector<unsigned char> snapshot() { assert(false); return std::vector<unsigned char>(); }
+    virtual void restore(const void *, size_t) { assert(false); }
 
     opts_init_t<real_t> *opts_init = nullptr;        // points at the live internal copy (particles.hpp:129)
     virtual ~particles_proto_t() {}
@@ -292,6 +297,16 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_outbuf(pimpl->h, &p, &n));
       return const_cast<real_t *>(static_cast<const real_t *>(p));
     }
+    std::vector<unsigned char> snapshot() override
+    {
+      size_t n = 0;
+      detail::lcx_check(lcx_snapshot_size(pimpl->h, &n));
+      std::vector<unsigned char> blob(n);
+      detail::lcx_check(lcx_snapshot_save(pimpl->h, blob.data(), blob.size(), &n));
+      blob.resize(n);
+      return blob;
+    }
+    void restore(const void *blob, size_t bytes) override { detail::lcx_check(lcx_snapshot_load(pimpl->h, blob, bytes)); }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

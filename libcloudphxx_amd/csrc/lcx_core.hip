@@ -25,7 +25,9 @@
 #include "../../include/lcx.h"
 #include "../../include/lcx_rlx.h"
 #include "../../include/lcx_chem.h"
+#include "../../include/lcx_state.h"
 #include "lcx_kernels.hpp"
+#include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
 
 // every kernel launch of this translation unit and every host wait for a stream are COUNTED (lcx_get_state_u64 "raw_launches"): what a
@@ -157,6 +159,11 @@ struct IParticles {
   virtual void x_sort_interior() { no_exch(); }
   virtual bool x_finish(const lcx_opts_t &, unsigned *) { no_exch(); }
   virtual void *stream() { return nullptr; }
+  // checkpoint and restart (include/lcx_state.h): built for a single-device object without neighbours
+  [[noreturn]] static void no_snapshot() { throw std::runtime_error("libcloudph++: snapshot of a decomposed domain is not built"); }
+  virtual size_t snapshot_size() { no_snapshot(); }
+  virtual size_t snapshot_save(void *, size_t) { no_snapshot(); }
+  virtual void snapshot_load(const void *, size_t) { no_snapshot(); }
 };
 
 // ---- host-side spectrum analysis shared by the object and by the entries that need no device (lcx_rlx_layout) ----
@@ -3318,6 +3325,349 @@ struct Particles : IParticles {
       post_copy_after_fused_move(opts);
     } else { reused_total = 0; post_copy(opts); }
   }
+
+  // ------------------------------------------------------------------------------------------
+  // checkpoint and restart (include/lcx_state.h)
+  // ------------------------------------------------------------------------------------------
+  // The storage is saved AS IT IS -- its whole extent with the dead slots, the cell order as the last sort or scatter left it, the
+  // arrival ranks of a deferred scatter -- together with every flag, counter and drawn salt that says what is still owed: nothing is
+  // settled, compacted or re-sorted on the way, so the object that took a snapshot and the object restored from it go on as an
+  // object that did neither.  One list of scalars and one list of device arrays serve saving, loading and sizing alike.
+  // ---- the scalars: f(name, member) ----
+  template <class F> void snap_scalars(F &&f)
+  {
+    f("n_part", npart); f("n_storage", nphys); f("sort_base", sort_base); f("steps_since_reorder", steps_since_reorder);
+    f("rng_call", rng_call); f("src_stp_ctr", src_stp_ctr); f("rlx_stp_ctr", rlx_stp_ctr); f("tag_next", tag_next);
+    f("cells_version", cells_version); f("meta_version", meta_version); f("big_n", big_n); f("big_mx", big_mx); f("big_thr", big_thr);
+    f("sstp_cond", sstp_cond); f("sstp_cond_act", sstp_cond_act); f("sstp_coal", sstp_coal); f("sstp_chem", sstp_chem); f("dt", dt);
+    f("adve_scheme", adve_scheme); f("n_cx", n_cx); f("n_cy", n_cy); f("n_cz", n_cz);
+    f("var_rho", var_rho); f("sorted", sorted); f("sorted_shuffled", sorted_shuffled); f("shuffle_fresh", shuffle_fresh); f("last_async_coal", last_async_coal);
+    f("coal_marks_dead", coal_marks_dead); f("zero_n_unmarked", zero_n_unmarked); f("eager_compact", eager_compact); f("replay_used", replay_used);
+    f("sort_deferred", sort_deferred); f("deferred_shuffle", deferred_shuffle); f("rank_owed", rank_owed);
+    f("deferred_rs.call", deferred_rs.call); f("deferred_rs.seed", deferred_rs.seed); f("deferred_rs.s1", deferred_rs.s1); f("deferred_rs.s2", deferred_rs.s2);
+    f("last_shuffle_rs.call", last_shuffle_rs.call); f("last_shuffle_rs.seed", last_shuffle_rs.seed); f("last_shuffle_rs.s1", last_shuffle_rs.s1); f("last_shuffle_rs.s2", last_shuffle_rs.s2);
+    f("vtpre_valid", vtpre_valid); f("vt_fix_pending", vt_fix_pending); f("count_mom_valid_all", count_mom_valid_all);
+    f("kpa_uniform", kpa_uniform); f("kpa_value", kpa_value); f("n_max_stale", n_max_stale); f("coal_bound_armed", coal_bound_armed);
+    f("listed_from_hist", listed_from_hist); f("meta_known_valid", meta_known_valid); f("meta_known_v0", meta_known_v[0]); f("meta_known_v1", meta_known_v[1]);
+    f("turb_adve_now", turb_adve_now); f("last_cond_kernel", last_cond_kernel); f("last_coal_kernel", last_coal_kernel);
+    f("log_rd_min", log_rd_min); f("log_rd_max", log_rd_max); f("multiplier", multiplier);
+    static const char *const pn[LCX_OUT_COUNT] = {"puddle.HNO3", "puddle.NH3", "puddle.CO2", "puddle.SO2", "puddle.H2O2", "puddle.O3", "puddle.S_VI", "puddle.H",
+      "puddle.liq_vol", "puddle.dry_vol", "puddle.prtcl_num", "puddle.ice_mass", "puddle.liq_num", "puddle.ice_num"};
+    for (int i = 0; i < LCX_OUT_COUNT; ++i) f(pn[i], puddle[i]);
+  }
+  // ---- the device arrays: f(name, buffer, elements, element type) -- a buffer that is not allocated, or of no elements, is left out ----
+  template <class F> void snap_arrays(F &&f)
+  {
+    const size_t n = nphys;
+    f("n", A.n, n, snap::ELEM_UINT); f("rd3", A.rd3, n, snap::ELEM_REAL); f("rw2", A.rw2, n, snap::ELEM_REAL); f("kappa", A.kpa, n, snap::ELEM_REAL);
+    f("vt", A.vt, n, snap::ELEM_REAL);
+    if (o.nx) f("x", A.x, n, snap::ELEM_REAL);
+    if (o.ny) f("y", A.y, n, snap::ELEM_REAL);
+    if (o.nz) f("z", A.z, n, snap::ELEM_REAL);
+    static const char *const chem_names[CH_ALL] = {"HNO3", "NH3", "CO2", "SO2", "H2O2", "O3", "S_VI", "H"};
+    for (int e = 0; e < n_ext; ++e) {
+      std::string nm = "ext" + std::to_string(e);
+      if (e == ix_rv) nm = "sstp_tmp_rv"; else if (e == ix_th) nm = "sstp_tmp_th"; else if (e == ix_rh) nm = "sstp_tmp_rh"; else if (e == ix_p) nm = "sstp_tmp_p";
+      else if (e == ix_rc2) nm = "rc2"; else if (e == ix_up) nm = "up"; else if (e == ix_vp) nm = "vp"; else if (e == ix_wp) nm = "wp"; else if (e == ix_ssp) nm = "ssp";
+      else if (e == ix_dot_ssp) nm = "dot_ssp"; else if (e == ix_ict) nm = "incloud_time"; else if (e == ix_tag) nm = "tag";
+      else if (ix_chem >= 0 && e >= ix_chem && e < ix_chem + CH_ALL) nm = std::string("chem_") + chem_names[e - ix_chem];
+      else if (e == ix_chem_V) nm = "chem_V"; else if (e == ix_chem_flag) nm = "chem_flag";
+      f(("sd." + nm).c_str(), A.ext[e], n, snap::ELEM_REAL);
+    }
+    f("ijk", ijk, n, snap::ELEM_UINT); f("rank", rank, n, snap::ELEM_UINT); f("sorted_id", sorted_id, n, snap::ELEM_UINT); f("sorted_ijk", sorted_ijk, n, snap::ELEM_UINT);
+    f("cell_cnt", cell_cnt, ncell, snap::ELEM_UINT); f("cell_start", cell_start, ncell + 1, snap::ELEM_UINT);
+    f("big_list", big_list, ncell + 1, snap::ELEM_UINT); f("step_cnt", step_cnt, 8, snap::ELEM_UINT); f("d_flag", d_flag, 1, snap::ELEM_UINT);
+    f("coal_cmax", coal_cmax, 2 * ncell, snap::ELEM_UINT); f("coal_n_max", coal_n_max, 1, snap::ELEM_UINT);
+    f("cell.th", th, ncell, snap::ELEM_REAL); f("cell.rv", rv, ncell, snap::ELEM_REAL); f("cell.rhod", rhod, ncell, snap::ELEM_REAL); f("cell.p", p, ncell, snap::ELEM_REAL);
+    f("cell.T", Tk, ncell, snap::ELEM_REAL); f("cell.RH", RH, ncell, snap::ELEM_REAL); f("cell.eta", eta, ncell, snap::ELEM_REAL); f("cell.dv", dv, ncell, snap::ELEM_REAL);
+    f("cell.lambda_D", lambda_D, ncell, snap::ELEM_REAL); f("cell.lambda_K", lambda_K, ncell, snap::ELEM_REAL);
+    f("cell.sstp_tmp_rv", sstp_tmp_rv, ncell, snap::ELEM_REAL); f("cell.sstp_tmp_th", sstp_tmp_th, ncell, snap::ELEM_REAL); f("cell.sstp_tmp_rh", sstp_tmp_rh, ncell, snap::ELEM_REAL);
+    f("cell.rw_mom3", rw_mom3, ncell, snap::ELEM_REAL);
+    f("cell.diss_rate", diss_rate, ncell, snap::ELEM_REAL); f("cell.tau", tau_cell, ncell, snap::ELEM_REAL); f("cell.tau_rlx", tau_rlx, ncell, snap::ELEM_REAL);
+    f("cell.vt_pre", vt_pre, ncell, snap::ELEM_BYTES);
+    f("courant_x", courant_x, n_cx, snap::ELEM_REAL); f("courant_y", courant_y, n_cy, snap::ELEM_REAL); f("courant_z", courant_z, n_cz, snap::ELEM_REAL);
+    f("puddle_acc", puddle_acc, 4, snap::ELEM_REAL); f("puddle_sum", puddle_sum, 4 + 256 * 4, snap::ELEM_REAL);
+    for (int gs = 0; gs < CH_GAS; ++gs) {
+      f((std::string("ambient.") + chem_names[gs]).c_str(), amb[gs], ncell, snap::ELEM_REAL);
+      f((std::string("ambient_tmp.") + chem_names[gs]).c_str(), amb_tmp[gs], ncell, snap::ELEM_REAL);
+    }
+    f("puddle_chem", puddle_chem, size_t(CH_ALL), snap::ELEM_REAL);
+  }
+  // ---- every scalar field of the options an object is created with (pointers and callbacks left out): f(name, field) ----
+  template <class F> static void snap_opts(const lcx_opts_init_t &q, F &&f)
+  {
+#define LCX_SNAP_OPT(x) f(#x, q.x)
+    LCX_SNAP_OPT(nx); LCX_SNAP_OPT(ny); LCX_SNAP_OPT(nz); LCX_SNAP_OPT(dx); LCX_SNAP_OPT(dy); LCX_SNAP_OPT(dz); LCX_SNAP_OPT(dt);
+    LCX_SNAP_OPT(sstp_cond); LCX_SNAP_OPT(sstp_coal); LCX_SNAP_OPT(sstp_cond_act); LCX_SNAP_OPT(sstp_chem);
+    LCX_SNAP_OPT(x0); LCX_SNAP_OPT(y0); LCX_SNAP_OPT(z0); LCX_SNAP_OPT(x1); LCX_SNAP_OPT(y1); LCX_SNAP_OPT(z1);
+    LCX_SNAP_OPT(sd_conc); LCX_SNAP_OPT(sd_conc_large_tail); LCX_SNAP_OPT(aerosol_independent_of_rhod); LCX_SNAP_OPT(variable_dt_switch);
+    LCX_SNAP_OPT(sd_const_multi); LCX_SNAP_OPT(n_sd_max); LCX_SNAP_OPT(kernel); LCX_SNAP_OPT(terminal_velocity); LCX_SNAP_OPT(adve_scheme); LCX_SNAP_OPT(RH_formula);
+    LCX_SNAP_OPT(n_kernel_parameters); LCX_SNAP_OPT(chem_switch); LCX_SNAP_OPT(coal_switch); LCX_SNAP_OPT(sedi_switch); LCX_SNAP_OPT(subs_switch); LCX_SNAP_OPT(rlx_switch);
+    LCX_SNAP_OPT(turb_adve_switch); LCX_SNAP_OPT(turb_cond_switch); LCX_SNAP_OPT(turb_coal_switch); LCX_SNAP_OPT(ice_switch); LCX_SNAP_OPT(exact_sstp_cond);
+    LCX_SNAP_OPT(sstp_cond_mix); LCX_SNAP_OPT(adaptive_sstp_cond); LCX_SNAP_OPT(time_dep_ice_nucl); LCX_SNAP_OPT(RH_max);
+    LCX_SNAP_OPT(sstp_cond_adapt_drw2_eps); LCX_SNAP_OPT(sstp_cond_adapt_drw2_max); LCX_SNAP_OPT(rc2_T);
+    LCX_SNAP_OPT(rng_seed); LCX_SNAP_OPT(rng_seed_init); LCX_SNAP_OPT(rng_seed_init_switch); LCX_SNAP_OPT(dev_count); LCX_SNAP_OPT(dev_id);
+    LCX_SNAP_OPT(n_w_LS); LCX_SNAP_OPT(n_SGS_mix_len); LCX_SNAP_OPT(n_aerosol_conc_factor); LCX_SNAP_OPT(rd_min); LCX_SNAP_OPT(rd_max);
+    LCX_SNAP_OPT(no_ccn_at_init); LCX_SNAP_OPT(open_side_walls); LCX_SNAP_OPT(periodic_topbot_walls); LCX_SNAP_OPT(src_type); LCX_SNAP_OPT(th_dry); LCX_SNAP_OPT(const_p);
+    LCX_SNAP_OPT(diag_incloud_time); LCX_SNAP_OPT(n_dry_distros); LCX_SNAP_OPT(n_dry_sizes); LCX_SNAP_OPT(n_x_tot); LCX_SNAP_OPT(n_x_bfr); LCX_SNAP_OPT(bcond_lft);
+    LCX_SNAP_OPT(bcond_rgt); LCX_SNAP_OPT(strict_fp); LCX_SNAP_OPT(cond_solver); LCX_SNAP_OPT(reorder_every); LCX_SNAP_OPT(stream_ordered); LCX_SNAP_OPT(dbg_flags);
+    LCX_SNAP_OPT(dbg_cond_budget); LCX_SNAP_OPT(dbg_pack_delay_us); LCX_SNAP_OPT(dbg_flags2);
+    LCX_SNAP_OPT(src_x0); LCX_SNAP_OPT(src_y0); LCX_SNAP_OPT(src_z0); LCX_SNAP_OPT(src_x1); LCX_SNAP_OPT(src_y1); LCX_SNAP_OPT(src_z1);
+    LCX_SNAP_OPT(rlx_bins); LCX_SNAP_OPT(supstp_rlx); LCX_SNAP_OPT(rlx_sd_per_bin); LCX_SNAP_OPT(rlx_timescale); LCX_SNAP_OPT(n_rlx_dry_distros); LCX_SNAP_OPT(chem_rho);
+#undef LCX_SNAP_OPT
+  }
+  // a member <-> the 64 bits it is stored in: integers as they are (signed ones sign-extended), reals as a double's bit pattern
+  static uint64_t snap_bits(bool v) { return v ? 1 : 0; }
+  static uint64_t snap_bits(int v) { return uint64_t(int64_t(v)); }
+  static uint64_t snap_bits(unsigned v) { return v; }
+  static uint64_t snap_bits(unsigned long v) { return v; }
+  static uint64_t snap_bits(unsigned long long v) { return v; }
+  static uint64_t snap_bits(double v) { uint64_t b; memcpy(&b, &v, 8); return b; }
+  static uint64_t snap_bits(float v) { return snap_bits(double(v)); }
+  static void snap_unbits(uint64_t b, bool &v) { v = b != 0; }
+  static void snap_unbits(uint64_t b, int &v) { v = int(int64_t(b)); }
+  static void snap_unbits(uint64_t b, unsigned &v) { v = unsigned(b); }
+  static void snap_unbits(uint64_t b, unsigned long &v) { v = (unsigned long)b; }
+  static void snap_unbits(uint64_t b, unsigned long long &v) { v = b; }
+  static void snap_unbits(uint64_t b, double &v) { memcpy(&v, &b, 8); }
+  static void snap_unbits(uint64_t b, float &v) { double d; memcpy(&d, &b, 8); v = float(d); }
+
+  // loading: the object is fresh, only the scope is checked
+  void snap_refuse_unless_quiet(bool loading = false)
+  {
+    if (distmem()) throw lcx_error("libcloudph++: snapshot of a decomposed domain is not built");
+    if (loading) return;
+    if (!init_called) throw lcx_error("libcloudph++: a snapshot is taken after init() or after step_async(); this object has not been initialised");
+    if (should_now_run_async || should_now_run_cond)
+      throw lcx_error("libcloudph++: a snapshot is taken after init() or after step_async(), not between step_sync() and step_async()");
+    if (lft_count || rgt_count || fused_pending) throw lcx_error("libcloudph++: a snapshot cannot be taken while the neighbour exchange of this step is pending");
+    if (!replay.empty()) throw lcx_error("libcloudph++: a snapshot cannot be taken while replayed random numbers are queued (the replay queue is not empty)");
+  }
+  snap::layout snap_layout()
+  {
+    snap::layout L;
+    L.real_kind = uint32_t(sizeof(T)); L.lib_version = lcx_version();
+    snap_opts(o, [&](const char *nm, auto v) { L.add_opt(nm, snap_bits(v)); });
+    snap_scalars([&](const char *nm, auto &v) { L.add_scalar(nm, snap_bits(v)); });
+    L.add_scalar("n_cell", ncell);
+    snap_arrays([&](const char *nm, auto &buf, size_t count, uint32_t type) {
+      if (buf.p && count) L.add_section(nm, type, uint32_t(sizeof(*buf.p)), count);
+    });
+    L.finish();
+    return L;
+  }
+  // two page-locked chunks between the device and the caller's (possibly pageable) buffer: the copy of one chunk runs while the host
+  // moves the other.  Never a blob-sized allocation, pinned or on the device.
+  struct SnapStager {
+    hipStream_t st; size_t chunk; void *pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Pend { void *dst = nullptr; size_t n = 0; bool busy = false; } pend[2];
+    unsigned k = 0;
+    SnapStager(hipStream_t s, size_t chunk_) : st(s), chunk(chunk_)
+    {
+      for (int i = 0; i < 2; ++i) { HIPCHK(hipHostMalloc(&pin[i], chunk, hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+    }
+    ~SnapStager()
+    {
+      (void)hipStreamSynchronize(st);
+      for (int i = 0; i < 2; ++i) { if (pin[i]) (void)hipHostFree(pin[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
+    }
+    void drain(int s)
+    {
+      if (!pend[s].busy) return;
+      HIPCHK(hipEventSynchronize(ev[s]));
+      if (pend[s].dst) memcpy(pend[s].dst, pin[s], pend[s].n);
+      pend[s].busy = false;
+    }
+    void d2h(void *dst, const void *src, size_t bytes)
+    {
+      for (size_t off = 0; off < bytes; off += chunk) {
+        const size_t n = std::min(chunk, bytes - off); const int s = int(k++ & 1u);
+        drain(s);
+        HIPCHK(hipMemcpyAsync(pin[s], (const char *)src + off, n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(ev[s], st));
+        pend[s].dst = (char *)dst + off; pend[s].n = n; pend[s].busy = true;
+      }
+    }
+    void h2d(void *dst, const void *src, size_t bytes)
+    {
+      for (size_t off = 0; off < bytes; off += chunk) {
+        const size_t n = std::min(chunk, bytes - off); const int s = int(k++ & 1u);
+        drain(s);
+        memcpy(pin[s], (const char *)src + off, n);
+        HIPCHK(hipMemcpyAsync((char *)dst + off, pin[s], n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(ev[s], st));
+        pend[s].dst = nullptr; pend[s].n = n; pend[s].busy = true;
+      }
+    }
+    void finish() { drain(0); drain(1); }
+  };
+  DevBuf<uint64_t> snap_cks;       // [0, CKS_MAX_BLOCKS): the partials of one section, behind them one result per section
+  // queues the checksum of a device array on the stream; result -> snap_cks[CKS_MAX_BLOCKS + slot]
+  void snap_checksum_async(const void *dev, size_t bytes, size_t slot)
+  {
+    const unsigned blocks = cks_blocks(bytes);
+    hipLaunchKernelGGL(k_checksum64, dim3(blocks), dim3(CKS_BS), 0, st, (const unsigned char *)dev, bytes, snap_cks.p);
+    hipLaunchKernelGGL(k_checksum64_fold, dim3(1), dim3(CKS_BS), 0, st, (const uint64_t *)snap_cks.p, blocks, snap_cks.p + CKS_MAX_BLOCKS + slot);
+  }
+  size_t snapshot_size() override { snap_refuse_unless_quiet(); return size_t(snap_layout().total_bytes); }
+  size_t snapshot_save(void *buf, size_t capb) override
+  {
+    snap_refuse_unless_quiet();
+    sync();                                    // (joins a ranking on its own stream; nothing of the step is in flight behind this)
+    snap::layout L = snap_layout();
+    if (!buf || capb < L.total_bytes) throw lcx_error("libcloudph++: snapshot buffer too small (" + std::to_string(capb) + " bytes, " + std::to_string(L.total_bytes) + " needed)");
+    unsigned char *b = static_cast<unsigned char *>(buf);
+    snap_cks.alloc(size_t(CKS_MAX_BLOCKS) + L.sections.size() + 1);
+    {
+      SnapStager sg(st, size_t(snap::CHUNK_BYTES));
+      size_t slot = 0;
+      snap_arrays([&](const char *, auto &dbuf, size_t count, uint32_t) {
+        if (!dbuf.p || !count) return;
+        const snap::section &s = L.sections[slot];
+        const size_t bytes = count * sizeof(*dbuf.p);
+        snap_checksum_async(dbuf.p, bytes, slot);        // while the data is in HBM, ahead of its copy on the same stream
+        sg.d2h(b + s.offset, dbuf.p, bytes);
+        memset(b + s.offset + bytes, 0, size_t(snap::align_up(s.offset + bytes) - (s.offset + bytes)));
+        ++slot;
+      });
+      sg.finish();
+    }
+    if (!L.sections.empty()) {
+      std::vector<uint64_t> sums = d2h(snap_cks.p + CKS_MAX_BLOCKS, L.sections.size());
+      for (size_t i = 0; i < sums.size(); ++i) L.sections[i].checksum = sums[i];
+    }
+    L.write_head(b);
+    return size_t(L.total_bytes);
+  }
+  // in the place of init(): what init() does without sampling, then the saved state
+  void snapshot_load(const void *buf, size_t bytes) override
+  {
+    snap_refuse_unless_quiet(true);
+    if (init_called) throw lcx_error("libcloudph++: init() may be called just once (a snapshot is restored into a fresh object, in the place of init())");
+    snap::view V; std::string err;
+    if (!snap::validate(buf, bytes, V, err)) throw lcx_error(err);
+    if (std::string(V.h.lib_version) != lcx_version())
+      throw lcx_error(std::string("libcloudph++: snapshot was written by another library version (\"") + V.h.lib_version + "\", this is \"" + lcx_version() + "\")");
+    if (V.h.real_kind != sizeof(T))
+      throw lcx_error("libcloudph++: snapshot differs from this object in real_kind (" + std::to_string(V.h.real_kind) + " in the snapshot, " + std::to_string(sizeof(T)) + " here)");
+    {                                          // the options: the first field that differs is named (dev_id says where the object runs, not what it computes)
+      std::string bad;
+      snap_opts(o, [&](const char *nm, auto v) {
+        if (!bad.empty() || std::string(nm) == "dev_id") return;
+        const snap::named_value *e = V.find(V.opts, nm);
+        if (!e) bad = std::string("libcloudph++: snapshot lacks the option ") + nm;
+        else if (e->bits != snap_bits(v)) {
+          decltype(v) theirs; snap_unbits(e->bits, theirs);
+          bad = std::string("libcloudph++: snapshot differs from this object in opts_init.") + nm + " (" + std::to_string(theirs) + " in the snapshot, " + std::to_string(v) + " here)";
+        }
+      });
+      if (!bad.empty()) throw lcx_error(bad);
+    }
+    // every scalar must be there, every section must be one that this object has, of this object's element size and of the count that the scalars imply
+    auto scalar_of = [&](const char *nm) -> uint64_t {
+      const snap::named_value *e = V.find(V.scalars, nm);
+      if (!e) throw lcx_error(std::string("libcloudph++: snapshot lacks the scalar ") + nm);
+      return e->bits;
+    };
+    snap_scalars([&](const char *nm, auto &) { (void)scalar_of(nm); });
+    if (scalar_of("n_cell") != ncell) throw lcx_error("libcloudph++: snapshot differs from this object in the number of cells");
+    if (scalar_of("n_storage") > cap || scalar_of("n_part") > scalar_of("n_storage")) throw lcx_error("libcloudph++: snapshot holds more super-droplets than n_sd_max");
+    if (scalar_of("sort_base") != 0) throw lcx_error("libcloudph++: snapshot of a decomposed domain is not built");
+    // (from here on host members change; a failure puts them back and leaves the object uninitialised, ready for another load)
+    std::vector<uint64_t> before;
+    snap_scalars([&](const char *, auto &v) { before.push_back(snap_bits(v)); });
+    auto roll_back = [&]() {
+      size_t i = 0;
+      snap_scalars([&](const char *, auto &v) { snap_unbits(before[i++], v); });
+      init_called = false;
+      (void)hipStreamSynchronize(st);
+      snap_rezero();
+    };
+    try {
+      snap_scalars([&](const char *nm, auto &v) { snap_unbits(scalar_of(nm), v); });
+      const int nxh = o.nx + 2 * halo;
+      size_t want_cx = 0, want_cy = 0, want_cz = 0;
+      switch (n_dims) {
+        case 3: want_cx = size_t(nxh + 1) * o.ny * o.nz; want_cy = size_t(nxh) * (o.ny + 1) * o.nz; want_cz = size_t(nxh) * o.ny * (o.nz + 1); break;
+        case 2: want_cx = size_t(nxh + 1) * o.nz; want_cz = size_t(nxh) * (o.nz + 1); break;
+        case 1: want_cx = size_t(nxh) + 1; break;
+        default: break;
+      }
+      if (n_cx != want_cx || n_cy != want_cy || n_cz != want_cz) throw lcx_error("libcloudph++: snapshot differs from this object in the extent of the Courant arrays");
+      std::vector<char> seen(V.sections.size(), 0);
+      // pass 1: nothing on the device is touched
+      snap_arrays([&](const char *nm, auto &dbuf, size_t count, uint32_t type) {
+        const snap::section *s = V.find_section(nm);
+        if (!s) return;
+        seen[size_t(s - V.sections.data())] = 1;
+        if (s->elem_bytes != sizeof(*dbuf.p) || s->elem_type != type || s->count != count)
+          throw lcx_error(std::string("libcloudph++: snapshot section '") + nm + "' does not fit this object (" + std::to_string(s->count) + " elements of " +
+                          std::to_string(s->elem_bytes) + " bytes, " + std::to_string(count) + " of " + std::to_string(sizeof(*dbuf.p)) + " expected)");
+      });
+      for (size_t i = 0; i < seen.size(); ++i)
+        if (!seen[i]) throw lcx_error("libcloudph++: snapshot section '" + snap::get_name(V.sections[i].name) + "' is unknown to this object");
+      for (const char *must : {"n", "rd3", "rw2", "kappa", "vt", "ijk", "rank", "sorted_id", "sorted_ijk"})
+        if (nphys && !V.find_section(must)) throw lcx_error(std::string("libcloudph++: snapshot lacks the section '") + must + "'");
+      for (const char *must : {"cell_cnt", "cell_start", "cell.th", "cell.rv", "cell.rhod", "cell.p", "cell.T", "cell.RH", "cell.eta", "cell.dv", "puddle_acc"})
+        if (!V.find_section(must)) throw lcx_error(std::string("libcloudph++: snapshot lacks the section '") + must + "'");
+      // what init() does without sampling
+      init_called = true;
+      courant_x.alloc_zero(n_cx, st); courant_y.alloc_zero(n_cy, st); courant_z.alloc_zero(n_cz, st);
+      if (!w_LS_h.empty()) { std::vector<T> h(w_LS_h.begin(), w_LS_h.end()); w_LS.alloc(h.size()); h2d(w_LS.p, h.data(), h.size() * sizeof(T)); }
+      if (!conc_factor_h.empty()) { std::vector<T> h(conc_factor_h.begin(), conc_factor_h.end()); conc_factor.alloc(h.size()); h2d(conc_factor.p, h.data(), h.size() * sizeof(T)); }
+      if (o.coal_switch && !kparams.p) init_kernel();
+      if (o.terminal_velocity == LCX_VT_BEARD77FAST) {
+        vt_0.alloc(size_t(vtc.n_bin));
+        hipLaunchKernelGGL(k_init_vt0<T>, dim3(nblk(size_t(vtc.n_bin))), dim3(BS), 0, st, vt_0.p, vtc);
+      }
+      if (!B.n.p) alloc_attrs(B);
+      // pass 2: the sections, each checked against its checksum where it has landed
+      snap_cks.alloc(size_t(CKS_MAX_BLOCKS) + V.sections.size() + 1);
+      const unsigned char *b = static_cast<const unsigned char *>(buf);
+      {
+        SnapStager sg(st, size_t(snap::CHUNK_BYTES));
+        snap_arrays([&](const char *nm, auto &dbuf, size_t count, uint32_t) {
+          const snap::section *s = V.find_section(nm);
+          if (!s) return;
+          dbuf.alloc(count);
+          const size_t nb = count * sizeof(*dbuf.p);
+          sg.h2d(dbuf.p, b + s->offset, nb);
+          snap_checksum_async(dbuf.p, nb, size_t(s - V.sections.data()));
+        });
+        sg.finish();
+      }
+      if (!V.sections.empty()) {
+        std::vector<uint64_t> sums = d2h(snap_cks.p + CKS_MAX_BLOCKS, V.sections.size());
+        for (size_t i = 0; i < sums.size(); ++i)
+          if (sums[i] != V.sections[i].checksum)
+            throw lcx_error("libcloudph++: snapshot section '" + snap::get_name(V.sections[i].name) + "': checksum does not match (the blob is damaged)");
+      }
+      deferred_rs.un = nullptr; last_shuffle_rs.un = nullptr;
+      should_now_run_async = should_now_run_cond = selected_before_counting = false;
+      skip_pause = 0; skip_sample_pending = false; rank_pending = false;
+      sync();
+    } catch (...) { roll_back(); throw; }
+  }
+  // what the constructor left zero and a load that failed half-way may have written
+  void snap_rezero()
+  {
+    npart = nphys = 0;
+    for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0) (void)hipMemsetAsync(A.ext[ix].p, 0, cap * sizeof(T), st);
+    if (use_rc2) hipLaunchKernelGGL(k_fill<T>, dim3(nblk(cap)), dim3(BS), 0, st, A.ext[ix_rc2].p, cap, T(-1));
+    if (o.chem_switch) for (int e = ix_chem; e < ix_chem + CH_ALL + 2; ++e) (void)hipMemsetAsync(A.ext[e].p, 0, cap * sizeof(T), st);
+    (void)hipMemsetAsync(cell_cnt.p, 0, ncell * sizeof(uint32_t), st); (void)hipMemsetAsync(cell_start.p, 0, (ncell + 1) * sizeof(uint32_t), st);
+    (void)hipMemsetAsync(step_cnt.p, 0, 8 * sizeof(uint32_t), st); (void)hipMemsetAsync(d_flag.p, 0, sizeof(int), st); (void)hipMemsetAsync(puddle_acc.p, 0, 4 * sizeof(double), st);
+    for (DevBuf<T> *f : {&rhod, &th, &rv, &p, &Tk, &RH, &eta, &dv, &lambda_D, &lambda_K, &sstp_tmp_rv, &sstp_tmp_th, &sstp_tmp_rh, &rw_mom3, &count_mom})
+      (void)hipMemsetAsync(f->p, 0, ncell * sizeof(T), st);
+    if (diss_rate.p) (void)hipMemsetAsync(diss_rate.p, 0, ncell * sizeof(T), st);
+    if (tau_cell.p) { (void)hipMemsetAsync(tau_cell.p, 0, ncell * sizeof(T), st); (void)hipMemsetAsync(tau_rlx.p, 0, ncell * sizeof(T), st); }
+    if (o.chem_switch) {
+      for (int gs = 0; gs < CH_GAS; ++gs) { (void)hipMemsetAsync(amb[gs].p, 0, ncell * sizeof(T), st); if (amb_tmp[gs].p) (void)hipMemsetAsync(amb_tmp[gs].p, 0, ncell * sizeof(T), st); }
+      (void)hipMemsetAsync(puddle_chem.p, 0, CH_ALL * sizeof(double), st);
+    }
+    for (double &v : puddle) v = 0;
+    (void)hipStreamSynchronize(st);
+  }
 };
 
 } // namespace lcx
@@ -3546,6 +3896,71 @@ int lcx_math_probe(int which, const double *x, double *y, size_t n)
     const hipError_t e = hipMemcpy(y, d, n * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) throw std::runtime_error(std::string("libcloudph++ (HIP): math probe failed: ") + hipGetErrorString(e));
+  })
+}
+
+// ---- checkpoint and restart (include/lcx_state.h) ----
+int lcx_snapshot_size(lcx_particles *h, size_t *bytes) { LCX_TRY(*bytes = H->snapshot_size()) }
+int lcx_snapshot_save(lcx_particles *h, void *host_buf, size_t cap, size_t *written)
+{ LCX_TRY({ const size_t n = H->snapshot_save(host_buf, cap); if (written) *written = n; }) }
+int lcx_snapshot_load(lcx_particles *h, const void *host_buf, size_t bytes) { LCX_TRY(H->snapshot_load(host_buf, bytes)) }
+int lcx_snapshot_describe(const void *host_buf, size_t bytes, char *out, size_t cap)
+{
+  try {                                              // (host only: no device is looked for or bound)
+    lcx::snap::view v; std::string err;
+    if (!lcx::snap::validate(host_buf, bytes, v, err)) throw std::runtime_error(err);
+    const std::string text = lcx::snap::describe(v);
+    if (out && cap) { const size_t n = std::min(cap - 1, text.size()); memcpy(out, text.data(), n); out[n] = 0; }
+    if (out && cap <= text.size()) throw std::runtime_error("libcloudph++: lcx_snapshot_describe: the text takes " + std::to_string(text.size() + 1) + " bytes");
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; } catch (...) { g_err = "libcloudph++: unknown error"; return 1; }
+}
+int lcx_snapshot_checksum_host(const void *data, size_t bytes, unsigned long long *out)
+{
+  try { *out = lcx::snap::checksum64(data, bytes); return 0; }
+  catch (const std::exception &e) { g_err = e.what(); return 1; } catch (...) { g_err = "libcloudph++: unknown error"; return 1; }
+}
+int lcx_snapshot_checksum_probe(const void *host_data, size_t bytes, unsigned long long *out)
+{
+  LCX_TRY({
+    unsigned char *d = nullptr; uint64_t *part = nullptr;
+    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess || hipMalloc(&part, (size_t(lcx::CKS_MAX_BLOCKS) + 1) * sizeof(uint64_t)) != hipSuccess)
+    { (void)hipFree(d); throw std::runtime_error("libcloudph++ (HIP): hipMalloc failed"); }
+    if (bytes) (void)hipMemcpy(d, host_data, bytes, hipMemcpyHostToDevice);
+    const unsigned blocks = lcx::cks_blocks(bytes);
+    hipLaunchKernelGGL(lcx::k_checksum64, dim3(blocks), dim3(lcx::CKS_BS), 0, 0, (const unsigned char *)d, bytes, part);
+    hipLaunchKernelGGL(lcx::k_checksum64_fold, dim3(1), dim3(lcx::CKS_BS), 0, 0, (const uint64_t *)part, blocks, part + lcx::CKS_MAX_BLOCKS);
+    uint64_t r = 0;
+    const hipError_t e = hipMemcpy(&r, part + lcx::CKS_MAX_BLOCKS, sizeof r, hipMemcpyDeviceToHost);
+    (void)hipFree(d); (void)hipFree(part);
+    if (e != hipSuccess) throw std::runtime_error(std::string("libcloudph++ (HIP): checksum probe failed: ") + hipGetErrorString(e));
+    *out = r;
+  })
+}
+
+int lcx_snapshot_checksum_time(size_t bytes, int reps, double *ms_per_pass)
+{
+  LCX_TRY({
+    unsigned char *d = nullptr; uint64_t *part = nullptr; hipEvent_t a = nullptr; hipEvent_t b = nullptr;
+    if (reps < 1) throw std::runtime_error("libcloudph++: lcx_snapshot_checksum_time: reps < 1");
+    if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess || hipMalloc(&part, (size_t(lcx::CKS_MAX_BLOCKS) + 1) * sizeof(uint64_t)) != hipSuccess)
+    { (void)hipFree(d); throw std::runtime_error("libcloudph++ (HIP): hipMalloc failed"); }
+    (void)hipMemset(d, 0x5a, bytes);
+    (void)hipEventCreate(&a); (void)hipEventCreate(&b);
+    const unsigned blocks = lcx::cks_blocks(bytes);
+    auto pass = [&]() {
+      hipLaunchKernelGGL(lcx::k_checksum64, dim3(blocks), dim3(lcx::CKS_BS), 0, 0, (const unsigned char *)d, bytes, part);
+      hipLaunchKernelGGL(lcx::k_checksum64_fold, dim3(1), dim3(lcx::CKS_BS), 0, 0, (const uint64_t *)part, blocks, part + lcx::CKS_MAX_BLOCKS);
+    };
+    pass();                                          // (warm-up)
+    (void)hipEventRecord(a, 0);
+    for (int r = 0; r < reps; ++r) pass();
+    (void)hipEventRecord(b, 0);
+    const hipError_t e = hipEventSynchronize(b);
+    float ms = 0; (void)hipEventElapsedTime(&ms, a, b);
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipFree(d); (void)hipFree(part);
+    if (e != hipSuccess) throw std::runtime_error(std::string("libcloudph++ (HIP): checksum timing failed: ") + hipGetErrorString(e));
+    *ms_per_pass = double(ms) / reps;
   })
 }
 

@@ -425,6 +425,18 @@ def rlx_layout(opts_init, spectrum=0, lib=None):
     return edges, conc
 
 
+def snapshot_describe(buf, lib=None):
+    """what a snapshot() holds, as text (lcx_snapshot_describe, include/lcx_state.h; needs no GPU): the format and library versions,
+    the counts, one line per section.  Raises RuntimeError with the library's text for a blob that does not validate."""
+    lib = lib if lib is not None else _lib.load()
+    a = np.frombuffer(buf, dtype=np.uint8)
+    out = C.create_string_buffer(1 << 16)
+    if lib.lcx_snapshot_describe(C.c_void_p(a.ctypes.data if a.size else None), C.c_size_t(a.size), out, C.c_size_t(len(out))) != 0:
+        lib.lcx_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.lcx_last_error().decode())
+    return out.value.decode()
+
+
 class opts_t:
     """opts_t<real_t> (opts.hpp:20-50)."""
 
@@ -862,6 +874,24 @@ class particles_t:
         done = C.c_int()
         self._chk(self._f("exch_finish")(self._h, C.byref(oc), rec, C.byref(done)))
         return bool(done.value), list(rec)
+
+    # -- checkpoint and restart (include/lcx_state.h)
+    def snapshot(self):
+        """everything this object needs in order to go on, as one numpy array of uint8 (lcx_snapshot_save); taken after init() or after
+        step_async().  Taking it cannot be observed in this object's results."""
+        n = C.c_size_t()
+        self._chk(self._f("snapshot_size")(self._h, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        self._chk(self._f("snapshot_save")(self._h, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
+
+    def restore(self, buf):
+        """in the place of init(), on a fresh object made from the same opts_init and real_t: load a snapshot() (any object with the
+        buffer protocol) and be where the saved object was -- the next call is step_sync.  The caller keeps his own fields and step counter."""
+        a = np.frombuffer(buf, dtype=np.uint8)
+        if not a.flags["C_CONTIGUOUS"]:
+            a = np.ascontiguousarray(a)
+        self._chk(self._f("snapshot_load")(self._h, C.c_void_p(a.ctypes.data if a.size else None), C.c_size_t(a.size)))
 
     def stream(self):
         """the hipStream_t (as an integer) every launch of this object is queued on; 0 for an engine without one"""

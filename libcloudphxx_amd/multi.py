@@ -204,6 +204,13 @@ class particles_multi_t:
     def init(self, *a, **kw):
         self.prt.init(*a, **kw)
 
+    # checkpoint and restart is built for a single-device object without neighbours
+    def snapshot(self):
+        raise RuntimeError("libcloudph++: snapshot of a decomposed domain is not built")
+
+    def restore(self, buf):
+        raise RuntimeError("libcloudph++: snapshot of a decomposed domain is not built")
+
     def sync_in(self, *a, **kw):
         self.prt.sync_in(*a, **kw)
         self._exchange_courant_halo()
