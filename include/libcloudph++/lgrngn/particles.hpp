@@ -16,6 +16,7 @@
 #include "../../lcx.h"
 #include "../../lcx_chem.h"
 #include "../../lcx_state.h"
+#include "../../lcx_diag.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -84,6 +85,26 @@ namespace libcloudphxx { namespace lgrngn {
 
     opts_init_t<real_t> *opts_init = nullptr;        // points at the live internal copy (particles.hpp:129)
     virtual ~particles_proto_t() {}
+  };
+
+  // one request of particles_t<real_t, HIP>::diag_batch (an extension without a reference counterpart; include/lcx_diag.h): the chain
+  // "first clause, every further clause with _cons" and the count that follows it.  sel: LCX_DIAG_SEL_*, lo / hi as diag_*_rng take
+  // them; count: LCX_DIAG_SD_CONC or LCX_DIAG_*_MOM with k
+  template <typename real_t>
+  struct diag_req_t
+  {
+    struct clause_t { int sel; real_t lo, hi; };
+    std::vector<clause_t> clauses;
+    int count = LCX_DIAG_SD_CONC, k = 0;
+    diag_req_t &all() { clauses.push_back(clause_t{LCX_DIAG_SEL_ALL, 0, 0}); return *this; }
+    diag_req_t &water() { clauses.push_back(clause_t{LCX_DIAG_SEL_WATER, 0, 0}); return *this; }
+    diag_req_t &dry_rng(real_t a, real_t b) { clauses.push_back(clause_t{LCX_DIAG_SEL_DRY, a, b}); return *this; }
+    diag_req_t &wet_rng(real_t a, real_t b) { clauses.push_back(clause_t{LCX_DIAG_SEL_WET, a, b}); return *this; }
+    diag_req_t &kappa_rng(real_t a, real_t b) { clauses.push_back(clause_t{LCX_DIAG_SEL_KAPPA, a, b}); return *this; }
+    diag_req_t &sd_conc() { count = LCX_DIAG_SD_CONC; k = 0; return *this; }
+    diag_req_t &dry_mom(int k_) { count = LCX_DIAG_DRY_MOM; k = k_; return *this; }
+    diag_req_t &wet_mom(int k_) { count = LCX_DIAG_WET_MOM; k = k_; return *this; }
+    diag_req_t &kappa_mom(int k_) { count = LCX_DIAG_KAPPA_MOM; k = k_; return *this; }
   };
 
   namespace detail
@@ -307,6 +328,27 @@ namespace libcloudphxx { namespace lgrngn {
       return blob;
     }
     void restore(const void *blob, size_t bytes) override { detail::lcx_check(lcx_snapshot_load(pimpl->h, blob, bytes)); }
+    // EXTENSION, no reference counterpart (include/lcx_diag.h): out[r * stride + cell] = what reqs[r]'s selections, its count and
+    // outbuf() give, bit for bit, from one pass over the super-droplets per diag_batch_info() requests; stride >= n_cell.  The
+    // classic selection and outbuf() are left as they were.  Not virtual: particles_proto_t stays the reference's.
+    void diag_batch(const std::vector<diag_req_t<real_t>> &reqs, real_t *out, size_t stride, bool on_device = false)
+    {
+      std::vector<lcx_diag_req_t> c(reqs.size());
+      for (size_t r = 0; r < reqs.size(); ++r) {
+        const size_t nc = reqs[r].clauses.size();
+        c[r].n_clauses = nc > LCX_DIAG_MAX_CLAUSES ? LCX_DIAG_MAX_CLAUSES + 1 : int(nc);       // (too many: the library names the request)
+        for (size_t i = 0; i < nc && i < LCX_DIAG_MAX_CLAUSES; ++i)
+          c[r].clause[i] = lcx_diag_clause_t{reqs[r].clauses[i].sel, double(reqs[r].clauses[i].lo), double(reqs[r].clauses[i].hi)};
+        c[r].count = reqs[r].count; c[r].k = reqs[r].k;
+      }
+      detail::lcx_check(lcx_diag_batch(pimpl->h, c.data(), int(c.size()), out, stride, on_device ? 1 : 0));
+    }
+    int diag_batch_info(size_t *scratch_bytes = nullptr)
+    {
+      int rpp = 0;
+      detail::lcx_check(lcx_diag_batch_info(pimpl->h, &rpp, scratch_bytes));
+      return rpp;
+    }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

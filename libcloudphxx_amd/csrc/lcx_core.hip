@@ -26,6 +26,7 @@
 #include "../../include/lcx_rlx.h"
 #include "../../include/lcx_chem.h"
 #include "../../include/lcx_state.h"
+#include "../../include/lcx_diag.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -131,6 +132,9 @@ struct IParticles {
   virtual void diag_chem(int) { throw std::runtime_error("libcloudph++: chemistry is switched off in opts_init, but diag_chem was called"); }
   virtual size_t n_part() = 0;
   virtual size_t n_cell() = 0;
+  // many selections and moments in one pass (include/lcx_diag.h); the list has been validated
+  virtual void diag_batch(const lcx_diag_req_t *, int, void *, size_t, bool) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
+  virtual void diag_batch_info(int *, size_t *) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -511,6 +515,7 @@ struct Particles : IParticles {
     for (hipEvent_t e : prof_pool) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
     if (pinned) (void)hipHostFree(pinned);
+    if (diag_stage) (void)hipHostFree(diag_stage);
     if (skip_pinned) (void)hipHostFree(skip_pinned);
     if (ev_skip) (void)hipEventDestroy(ev_skip);
     // (the copy stream reads the staging areas: it is drained before they are freed)
@@ -2786,6 +2791,56 @@ struct Particles : IParticles {
                        T(T(4. / 3.) * cst<T>::rho_w * T(std::sqrt(M_PI / 2.))), count_mom.p);
     sync();
   }
+  // ---- lcx_diag_batch: a list of (selection chain, count) requests in passes of one launch each (k_diag_batch, lcx_diag_plan.hpp) ----
+  DevBuf<T> diag_res; void *diag_stage = nullptr; size_t diag_stage_rows = 0;
+  void diag_batch_info(int *req_per_pass, size_t *scratch_bytes) override
+  {
+    if (req_per_pass) *req_per_pass = diag::req_per_pass(ncell, sizeof(T));
+    if (scratch_bytes) *scratch_bytes = diag::scratch_bytes(ncell, sizeof(T));
+  }
+  void diag_batch(const lcx_diag_req_t *req, int n_req, void *out_, size_t stride, bool on_device) override
+  {
+    if (!out_) throw lcx_error("libcloudph++: diag_batch: out == NULL with n_req > 0");
+    if (stride < ncell) throw lcx_error("libcloudph++: diag_batch: req_stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
+    hskpng_sort();                                                     // (as diag_select and moms_sum: an object before init() answers as it does to diag_all)
+    const int rpp = diag::req_per_pass(ncell, sizeof(T));
+    const std::vector<diag::pass<T>> passes = diag::plan<T>(req, n_req, rpp, !on_device);
+    T *out = static_cast<T *>(out_);
+    if (!on_device) {
+      const size_t rows = size_t(std::min(n_req, rpp));
+      diag_res.alloc(rows * ncell);
+      if (rows > diag_stage_rows) {
+        if (diag_stage) { HIPCHK(hipHostFree(diag_stage)); diag_stage = nullptr; diag_stage_rows = 0; }
+        HIPCHK(hipHostMalloc(&diag_stage, rows * ncell * sizeof(T), hipHostMallocDefault));
+        diag_stage_rows = rows;
+      }
+    }
+    const uint32_t *order = sid();                                     // (pays an owed ranking, as moms_sum does)
+    // host output: a pass's rows come through the page-locked staging, which the next pass needs again.  The rows are moved on to the
+    // caller's array by a host function queued on the stream behind the copy, so the next pass's copy waits for it and the host waits once
+    std::vector<DiagScatter> jobs(on_device ? 0 : passes.size());
+    size_t j = 0;
+    try {
+      for (const diag::pass<T> &p : passes) {
+        hipLaunchKernelGGL(k_diag_batch<T>, dim3(nblk(ncell, cf_cells())), dim3(BS), 0, st, ncell, cf_cells(), cell_start.p, order, A.n.p, A.rd3.p, A.rw2.p, A.kpa.p,
+                           p.used, p.tab, p.n, m3_after.p, dv.p, rhod.p, n_dims, on_device ? out : diag_res.p, on_device ? stride : ncell);
+        if (on_device) continue;
+        HIPCHK(hipMemcpyAsync(diag_stage, diag_res.p, size_t(p.n) * ncell * sizeof(T), hipMemcpyDeviceToHost, st));
+        jobs[j] = DiagScatter{reinterpret_cast<char *>(out), static_cast<const char *>(diag_stage), p.src, p.n, stride * sizeof(T), ncell * sizeof(T)};
+        HIPCHK(hipLaunchHostFunc(st, &DiagScatter::run, &jobs[j]));
+        ++j;
+      }
+    } catch (...) { (void)hipStreamSynchronize(st); throw; }            // (a queued host function reads `jobs` and `passes`)
+    sync();
+  }
+  struct DiagScatter {
+    char *out; const char *stage; const int *src; int n; size_t out_row, stage_row;
+    static void run(void *self)
+    {
+      const DiagScatter &d = *static_cast<const DiagScatter *>(self);
+      for (int slot = 0; slot < d.n; ++slot) memcpy(d.out + size_t(d.src[slot]) * d.out_row, d.stage + size_t(slot) * d.stage_row, d.stage_row);
+    }
+  };
   void diag_sd_conc() override { moms_sum(A.rw2.p, T(0), 1, false); }
   void diag_mom(int attr, double power) override { moms_sum(attr_ptr(attr), T(power), 0, true); }
   void diag_precip_rate() override
@@ -3822,15 +3877,18 @@ int lcx_diag_RH(lcx_particles *h) { LCX_TRY(H->diag_cell(2)) }
 int lcx_diag_vel_div(lcx_particles *h) { LCX_TRY(H->diag_vel_div()) }
 int lcx_diag_all(lcx_particles *h) { LCX_TRY(H->diag_select(0, 0, 1, 0, 0)) }
 int lcx_diag_water(lcx_particles *h) { LCX_TRY(H->diag_select(2, 0, 1, 0, 0)) }
-int lcx_diag_dry_rng(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 0, 0, std::pow(a, 3), std::pow(b, 3))) }
-int lcx_diag_wet_rng(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 0, 1, std::pow(a, 2), std::pow(b, 2))) }
-int lcx_diag_kappa_rng(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 0, 2, a, b)) }
-int lcx_diag_dry_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 1, 0, std::pow(a, 3), std::pow(b, 3))) }
-int lcx_diag_wet_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 1, 1, std::pow(a, 2), std::pow(b, 2))) }
-int lcx_diag_kappa_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(H->diag_select(1, 1, 2, a, b)) }
-int lcx_diag_dry_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(0, k / 3.)) }
-int lcx_diag_wet_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(1, k / 2.)) }
-int lcx_diag_kappa_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(2, k)) }
+// (radii -> attribute units and k -> power by the functions that lcx_diag_batch plans with, lcx_diag_plan.hpp)
+static void diag_rng(IParticles *p, int sel, int cons, double a, double b)
+{ double lo, hi; lcx::diag::rng_bounds(sel, a, b, lo, hi); p->diag_select(1, cons, lcx::diag::sel_attr(sel), lo, hi); }
+int lcx_diag_dry_rng(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_DRY, 0, a, b)) }
+int lcx_diag_wet_rng(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_WET, 0, a, b)) }
+int lcx_diag_kappa_rng(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_KAPPA, 0, a, b)) }
+int lcx_diag_dry_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_DRY, 1, a, b)) }
+int lcx_diag_wet_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_WET, 1, a, b)) }
+int lcx_diag_kappa_rng_cons(lcx_particles *h, double a, double b) { LCX_TRY(diag_rng(H, LCX_DIAG_SEL_KAPPA, 1, a, b)) }
+int lcx_diag_dry_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(0, lcx::diag::mom_power(LCX_DIAG_DRY_MOM, k))) }
+int lcx_diag_wet_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(1, lcx::diag::mom_power(LCX_DIAG_WET_MOM, k))) }
+int lcx_diag_kappa_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(2, lcx::diag::mom_power(LCX_DIAG_KAPPA_MOM, k))) }
 int lcx_diag_incloud_time_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(4, k)) }
 int lcx_diag_up_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(5, k)) }
 int lcx_diag_vp_mom(lcx_particles *h, int k) { LCX_TRY(H->diag_mom(6, k)) }
@@ -3897,6 +3955,22 @@ int lcx_math_probe(int which, const double *x, double *y, size_t n)
     (void)hipFree(d);
     if (e != hipSuccess) throw std::runtime_error(std::string("libcloudph++ (HIP): math probe failed: ") + hipGetErrorString(e));
   })
+}
+
+// ---- many selections and moments in one pass (include/lcx_diag.h) ----
+int lcx_diag_batch_check(const lcx_diag_req_t *req, int n_req)
+{
+  std::string err;                                   // (host only: no device is looked for or bound)
+  if (lcx::diag::validate(req, n_req, err)) return 0;
+  g_err = err;
+  return 1;
+}
+int lcx_diag_batch_info(lcx_particles *h, int *req_per_pass, size_t *scratch_bytes) { LCX_TRY(H->diag_batch_info(req_per_pass, scratch_bytes)) }
+int lcx_diag_batch(lcx_particles *h, const lcx_diag_req_t *req, int n_req, void *out, size_t req_stride, int out_on_device)
+{
+  if (lcx_diag_batch_check(req, n_req)) return 1;
+  if (n_req == 0) return 0;
+  LCX_TRY(H->diag_batch(req, n_req, out, req_stride, out_on_device != 0))
 }
 
 // ---- checkpoint and restart (include/lcx_state.h) ----

@@ -12,6 +12,7 @@
 #pragma once
 #include "lcx_math.hpp"
 #include "lcx_cond_wq.hpp"
+#include "lcx_diag_plan.hpp"
 
 namespace lcx {
 
@@ -3133,14 +3134,16 @@ k_reorder(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, 
 // moments / diagnostics (moms.ipp:50-387, particles_diag.ipp)
 // ============================================================================================
 // n_filtered = f(n or n_filtered, vec)  mode: 0 all, 1 range [mn,mx), 2 vec > 0
+// (one selection step and one term of a moment as functions: k_diag_batch forms its weights and terms with the same two)
+template <class T> __device__ __forceinline__ T nfilt_step(int mode, T y, T v, T vmin, T vmax)
+{ return mode == 0 ? y : mode == 1 ? ((v >= vmin && v < vmax) ? y : T(0)) : y * (v > 0); }
+template <class T> __device__ __forceinline__ T mom_pow(T x, T power) { return x >= 0 ? pow(x, power) : pow(x, T(int(power))); }
 template <class T>
 __global__ void k_nfilt(size_t n_part, int mode, int cons, const n_t *n, const T *vec, T vmin, T vmax, T *nf)
 {
   const size_t i = gid(); if (i >= n_part) return;
   const T y = cons ? nf[i] : T(n[i]);
-  if (mode == 0) nf[i] = y;
-  else if (mode == 1) { const T v = vec[i]; nf[i] = (v >= vmin && v < vmax) ? y : T(0); }
-  else nf[i] = y * (vec[i] > 0);
+  nf[i] = nfilt_step(mode, y, mode == 0 ? T(0) : vec[i], vmin, vmax);
 }
 // selections by activation state (particles_diag.ipp:350-407): which 0: RH[cell] - S_cr >= 0, 1: rw2 >= rc2
 template <class T>
@@ -3175,7 +3178,7 @@ __global__ void k_mom_vals(size_t n_part, const uint32_t *sorted_id, const T *nf
   const uint32_t id = sorted_id[p];
   if (kind == 1) { out[p] = nf[id] > T(0) ? T(1) : T(0); return; }
   const T x = kind == 2 ? T(pow(vec[id], T(3. / 2)) * vec2[id]) : vec[id];
-  out[p] = x >= 0 ? nf[id] * pow(x, power) : nf[id] * pow(x, T(int(power)));
+  out[p] = nf[id] * mom_pow(x, power);
 }
 template <class T>
 __global__ void __launch_bounds__(BS)
@@ -3197,6 +3200,87 @@ k_cell_seqsum(size_t n_cell, int cfc, const uint32_t *cell_start, const T *vals,
     if (specific) { acc = acc / dv[c]; acc = acc / rhod[c]; }
   }
   out[c] = acc;
+}
+// lcx_diag_batch (include/lcx_diag.h): the per-cell sums of a pass of requests, each with the bits of k_nfilt ... k_nfilt, k_mom_vals,
+// k_cell_seqsum.  Grid and ranges as k_cell_seqsum.  A thread gathers n and the attributes that the pass reads ONCE, for its
+// CF_CAP / BS = 8 positions, and keeps them in registers for every request: nobody else reads a position's attributes, so LDS would
+// only hold what a register holds already, and staging all four columns in double (64 KiB + the 16 KiB of terms) would leave two
+// workgroups per CU where 16 KiB leaves ten.  Per request the terms go to LDS, one lane per cell adds its segment in sorted order
+// (seg_sum: first term, then +), divides and stores into the request's row.  Requests that follow each other with the same
+// (attribute, power) reuse the powers (same_pow; the host orders the pass so).  A range above CF_CAP (crowded cells, a single cell
+// above the cap) gathers anew for every request and lays its terms into ITS stretch [base, end) of `scratch` instead.
+template <class T> __device__ __forceinline__ T diag_weight(const diag::dev_req<T> &rq, T nn, T x0, T x1, T x2)
+{
+  T y = nn;
+  for (int cl = 0; cl < rq.n_clauses; ++cl) {
+    const int sel = rq.sel[cl];
+    if (sel == LCX_DIAG_SEL_ALL) continue;
+    const T v = sel == LCX_DIAG_SEL_DRY ? x0 : sel == LCX_DIAG_SEL_KAPPA ? x2 : x1;
+    y = nfilt_step(sel == LCX_DIAG_SEL_WATER ? 2 : 1, y, v, rq.lo[cl], rq.hi[cl]);
+  }
+  return y;
+}
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_diag_batch(size_t n_cell, int cfc, const uint32_t *cell_start, const uint32_t *sorted_id, const n_t *n, const T *rd3, const T *rw2, const T *kpa,
+             unsigned used, const diag::dev_pass<T> pass, int n_req, T *scratch, const T *dv, const T *rhod, int n_dims, T *out, size_t stride)
+{
+  __shared__ T lds[CF_CAP];
+  constexpr int PER = CF_CAP / BS;
+  const size_t c0 = size_t(blockIdx.x) * cfc;
+  const size_t c1 = c0 + cfc < n_cell ? c0 + cfc : n_cell;
+  const uint32_t base = cell_start[c0], end = cell_start[c1];
+  const bool staged = (end - base) <= uint32_t(CF_CAP);
+  const size_t c = c0 + threadIdx.x;
+  const bool owner = threadIdx.x < cfc && c < n_cell;
+  uint32_t s = 0, e = 0;
+  if (owner) { s = cell_start[c]; e = cell_start[c + 1]; }
+  T w[PER], x0[PER], x1[PER], x2[PER], pw[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const uint32_t q = base + threadIdx.x + uint32_t(k) * BS;
+    w[k] = x0[k] = x1[k] = x2[k] = pw[k] = T(0);
+    if (staged && q < end) {
+      const uint32_t id = sorted_id[q];
+      w[k] = T(n[id]);
+      if (used & 1u) x0[k] = rd3[id];
+      if (used & 2u) x1[k] = rw2[id];
+      if (used & 4u) x2[k] = kpa[id];
+    }
+  }
+  for (int r = 0; r < n_req; ++r) {
+    const diag::dev_req<T> &rq = pass.r[r];
+    const bool conc = rq.count == LCX_DIAG_SD_CONC;
+    const int a = rq.attr;
+    __syncthreads();                                                  // (the sums of the request before have read their terms)
+    if (staged) {
+#pragma unroll
+      for (int k = 0; k < PER; ++k) {
+        const uint32_t q = base + threadIdx.x + uint32_t(k) * BS;
+        if (q >= end) continue;
+        const T y = diag_weight(rq, w[k], x0[k], x1[k], x2[k]);
+        if (!conc && !rq.same_pow) pw[k] = mom_pow(a == 0 ? x0[k] : a == 2 ? x2[k] : x1[k], rq.power);
+        lds[q - base] = conc ? (y > T(0) ? T(1) : T(0)) : y * pw[k];
+      }
+    } else {
+      for (uint32_t q = base + threadIdx.x; q < end; q += BS) {
+        const uint32_t id = sorted_id[q];
+        const T v0 = (used & 1u) ? rd3[id] : T(0), v1 = (used & 2u) ? rw2[id] : T(0), v2 = (used & 4u) ? kpa[id] : T(0);
+        const T y = diag_weight(rq, T(n[id]), v0, v1, v2);
+        scratch[q] = conc ? (y > T(0) ? T(1) : T(0)) : y * mom_pow(a == 0 ? v0 : a == 2 ? v2 : v1, rq.power);
+      }
+      __threadfence_block();
+    }
+    __syncthreads();
+    if (owner) {
+      T acc = 0;
+      if (e > s) {
+        acc = seg_sum(lds, (const T *)scratch, staged, base, s, e);
+        if (!conc && n_dims > 0) { acc = acc / dv[c]; acc = acc / rhod[c]; }
+      }
+      out[size_t(rq.row) * stride + c] = acc;
+    }
+  }
 }
 // max over a cell of vec (diag_max_rw)
 template <class T>

@@ -238,6 +238,83 @@ class _arrinfo_c(C.Structure):
     _fields_ = [("data", C.c_void_p), ("strides", C.POINTER(C.c_ssize_t)), ("on_device", C.c_int)]
 
 
+# ---- many selections and moments in one pass (include/lcx_diag.h)
+DIAG_MAX_CLAUSES = 4
+_DIAG_SEL = {"all": 0, "dry": 1, "wet": 2, "kappa": 3, "water": 4}       # enum LCX_DIAG_SEL_*
+_DIAG_MOM = {"dry": 1, "wet": 2, "kappa": 3}                             # enum LCX_DIAG_*_MOM (0: LCX_DIAG_SD_CONC)
+
+
+class _diag_clause_c(C.Structure):
+    _fields_ = [("sel", C.c_int), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class _diag_req_c(C.Structure):
+    _fields_ = [("n_clauses", C.c_int), ("clause", _diag_clause_c * DIAG_MAX_CLAUSES), ("count", C.c_int), ("k", C.c_int)]
+
+
+def diag_batch_expressible(call):
+    """whether diag_batch serves (clauses, count): a chain of all / rng dry, wet, kappa / water selections, the first without _cons and
+    every further one with it, counted by sd_conc or a dry / wet / kappa moment"""
+    sel, cnt = call
+    if not 1 <= len(sel) <= DIAG_MAX_CLAUSES:
+        return False
+    for i, s in enumerate(sel):
+        if s[0] == "all":
+            cons = i > 0                                   # (diag_all has no _cons form: a later one would start the chain anew)
+            ok = len(s) == 1 and i == 0
+        elif s[0] == "rng":
+            ok, cons = len(s) == 5 and s[1] in _DIAG_MOM, bool(s[4]) if len(s) == 5 else None
+        elif s[0] == "water":
+            ok, cons = len(s) == 2, bool(s[1]) if len(s) == 2 else None
+        else:
+            return False
+        if not ok or cons != (i > 0):
+            return False
+    return (cnt[0] == "sd_conc" and len(cnt) == 1) or (cnt[0] == "mom" and len(cnt) == 3 and cnt[1] in _DIAG_MOM)
+
+
+def diag_batch_requests(reqs):
+    """[(clauses, count)] in the notation of the classic calls -- clauses: ("all",), ("rng", "dry" | "wet" | "kappa", lo, hi, cons),
+    ("water", cons); count: ("sd_conc",), ("mom", "dry" | "wet" | "kappa", k) -- as an array of lcx_diag_req_t"""
+    arr = (_diag_req_c * max(1, len(reqs)))()
+    for r, call in enumerate(reqs):
+        if not diag_batch_expressible(call):
+            raise ValueError("libcloudph++: diag_batch cannot express request %d: %r" % (r, call))
+        sel, cnt = call
+        arr[r].n_clauses = len(sel)
+        for i, s in enumerate(sel):
+            c = arr[r].clause[i]
+            c.sel = _DIAG_SEL[s[1]] if s[0] == "rng" else _DIAG_SEL[s[0]]
+            if s[0] == "rng":
+                c.lo, c.hi = float(s[2]), float(s[3])
+        arr[r].count, arr[r].k = (0, 0) if cnt[0] == "sd_conc" else (_DIAG_MOM[cnt[1]], int(cnt[2]))
+    return arr
+
+
+def diag_batch_calls(arr, n):
+    """the inverse of diag_batch_requests"""
+    sel_name = {v: k for k, v in _DIAG_SEL.items()}
+    mom_name = {v: k for k, v in _DIAG_MOM.items()}
+    reqs = []
+    for r in range(n):
+        sel = []
+        for i in range(arr[r].n_clauses):
+            c, cons = arr[r].clause[i], i > 0
+            nm = sel_name[c.sel]
+            sel.append(("all",) if nm == "all" else ("water", cons) if nm == "water" else ("rng", nm, c.lo, c.hi, cons))
+        reqs.append((sel, ("sd_conc",) if arr[r].count == 0 else ("mom", mom_name[arr[r].count], arr[r].k)))
+    return reqs
+
+
+def diag_batch_check(reqs, lib=None):
+    """lcx_diag_batch_check on a translated list or on an (array of lcx_diag_req_t, n) pair; needs no GPU.  Raises the library's text."""
+    lib = lib if lib is not None else _lib.load()
+    arr, n = reqs if isinstance(reqs, tuple) else (diag_batch_requests(reqs), len(reqs))
+    if lib.lcx_diag_batch_check(arr, C.c_int(n)) != 0:
+        lib.lcx_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.lcx_last_error().decode())
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -700,6 +777,39 @@ class particles_t:
     diag_vp_mom = _diagk("diag_vp_mom")
     diag_wp_mom = _diagk("diag_wp_mom")
     diag_water_cons = _diag0("diag_water_cons")
+
+    # -- many selections and moments in one pass (include/lcx_diag.h; no reference counterpart)
+    def diag_batch_info(self):
+        """(requests per pass, bytes that a diag_batch with host output allocates at most)"""
+        rpp, nb = C.c_int(), C.c_size_t()
+        self._chk(self._f("diag_batch_info")(self._h, C.byref(rpp), C.byref(nb)))
+        return rpp.value, nb.value
+
+    def diag_batch(self, reqs, out=None):
+        """what the loop `selections; count; outbuf()` over reqs gives, bit for bit, from one pass over the super-droplets per
+        diag_batch_info()[0] requests.  reqs: see diag_batch_requests.  Returns an (n_req, n_cell) array of real_t; with out= (a 2-D
+        numpy array, or a DeviceArray for memory of the object's device; unit stride along cells, row stride >= n_cell) fills and
+        returns that.  The classic selection and outbuf() are left as they were."""
+        arr, n_req = diag_batch_requests(reqs), len(reqs)
+        n_cell = self.n_cell
+        if out is None:
+            out = np.zeros((n_req, n_cell), dtype=self.real_t)
+        if len(out.shape) != 2 or out.shape[0] < n_req or out.shape[1] != n_cell:
+            raise RuntimeError("libcloudph++: diag_batch: out must be 2-D, (n_req, n_cell)")
+        on_device = isinstance(out, DeviceArray)
+        if on_device:
+            ptr, strides = out.ptr, out.strides
+        else:
+            if out.dtype != self.real_t:
+                raise RuntimeError("libcloudph++: array dtype does not match real_t")
+            if any(s % out.itemsize for s in out.strides) or not out.flags.writeable:
+                raise RuntimeError("libcloudph++: unsupported strides")
+            ptr, strides = out.ctypes.data, [s // out.itemsize for s in out.strides]
+        if n_cell > 1 and strides[1] != 1:
+            raise RuntimeError("libcloudph++: diag_batch: out must have unit stride along cells")
+        stride = strides[0] if out.shape[0] > 1 else n_cell                    # (a single row's stride says nothing)
+        self._chk(self._f("diag_batch")(self._h, arr, C.c_int(n_req), C.c_void_p(ptr), C.c_size_t(max(stride, 0)), C.c_int(int(on_device))))
+        return out
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
