@@ -233,8 +233,13 @@ enum lcx_dbg {
 #define LCX_DBG_NO_COAL_SKIP (1u << 31) /* coalescence that ranks for itself (k_coal_ranked) without the per-cell bound on the pairs' collision probability:
                                          * every pair's attributes are gathered, as in round 7 (the same bits; "raw_coal_skip") */
 enum lcx_dbg2 {
-  LCX_DBG2_COAL_SKIP_COUNT = 1 << 0    /* measurement / tests: k_coal_ranked counts the pairs it examines and the pairs it skips (two atomics per wave;
-                                        * lcx_get_state_u64 "raw_coal_skip" = { launches of the last lcx_step_async that used a bound, skipped, examined }) */
+  LCX_DBG2_COAL_SKIP_COUNT = 1 << 0,   /* measurement / tests: k_coal_ranked counts the pairs it examines and the pairs it skips (two atomics per wave;
+                                        * lcx_get_state_u64 "raw_coal_skip" = { launches of the last lcx_step_async that used a bound, skipped, examined })
+                                        * and its workgroups ("raw_coal_wg" = { workgroups that left before ranking, workgroups launched }, of those launches) */
+  LCX_DBG2_NO_COAL_RANK_EXIT = 1 << 1, /* k_coal_ranked with a bound ranks in every workgroup, as in round 8, instead of leaving ahead of the ranking where
+                                        * the workgroup keeps no pair (the same bits) */
+  LCX_DBG2_COAL_RANK_EXIT_ALWAYS = 1 << 2 /* tests: the form with the exit in every bound launch, also where the last launch's counters showed fewer than
+                                        * 0.24 of the workgroups leaving ("raw_coal_exit": launches of the last lcx_step_async in that form) */
 };
 
 /* lcx_get_state_u64("raw_mode") = { strict_fp, cond_solver, the kernel of the last condensation launch (below; 0: none yet), dbg_flags } as

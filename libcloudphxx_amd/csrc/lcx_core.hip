@@ -371,11 +371,21 @@ struct Particles : IParticles {
   bool n_max_stale = true;                   // ... to be recomputed: something other than coalescence has written multiplicities (init, set_particles,
                                              // a source, relaxation, recycling, immigrants) -- coalescence itself only lowers them
   DevBuf<T> coal_emax; int n_emax = 0;       // the efficiency table's running maximum by kernel_index (init_kernel); 0: no bound for this kernel
-  DevBuf<unsigned long long> coal_skip_cnt;  // LCX_DBG2_COAL_SKIP_COUNT: {pairs skipped, pairs examined} of the last step_async
+  DevBuf<unsigned long long> coal_skip_cnt;  // LCX_DBG2_COAL_SKIP_COUNT: {pairs skipped, pairs examined, workgroups that left before ranking, workgroups
+                                             // launched} of the last step_async ("raw_coal_skip", "raw_coal_wg")
+  unsigned long long coal_wg_no_exit = 0;    // (workgroups of its bound launches without the early exit, LCX_DBG2_NO_COAL_RANK_EXIT: that kernel counts none)
   // the bound pays only where it skips: a sample of the launch's counters comes back to the host without a wait (a copy and an event, polled by
   // the next step_async); below COAL_SKIP_MIN_SHARE^-1 of the pairs skipped, COAL_SKIP_PAUSE steps run without maxima and without bound, then
   // one step probes again.  Results do not depend on it: a launch with the bound and one without give the same bits.
   static constexpr int COAL_SKIP_PAUSE = 32; static constexpr unsigned long long COAL_SKIP_MIN_SHARE = 200;      // (0.5 %)
+  // Likewise the workgroups' exit ahead of the ranking (k_coal_ranked<.., SKIP, EXIT>): a workgroup that ranks after all pays for the vote and
+  // for id loads one level later -- +0.17 ms on a launch of the 128^3 x 64 box in which none leaves, against -0.53 ms where all do, so the exit
+  // breaks even at 0.17 / (0.17 + 0.53) = 0.24 of the workgroups leaving (EXPERIMENTS.md 7.10).  Below COAL_EXIT_MIN_PERCENT of them in a
+  // launch's counters (or the sample of them) the next COAL_EXIT_PAUSE bound launches take round 8's form, then one probes again.  The same
+  // bits either way.
+  static constexpr int COAL_EXIT_PAUSE = 32; static constexpr unsigned long long COAL_EXIT_MIN_PERCENT = 24;
+  int exit_pause = 0;
+  int last_coal_exit = 0;                    // ("raw_coal_exit": the coalescence launches of the last step_async in the EXIT form)
   DevBuf<unsigned long long> coal_skip_sample; void *skip_pinned = nullptr; hipEvent_t ev_skip = nullptr;
   bool skip_sample_pending = false; int skip_sample_n = 0, skip_pause = 0;
   void poll_skip_sample()
@@ -384,8 +394,12 @@ struct Particles : IParticles {
     skip_sample_pending = false;
     const unsigned long long *h = static_cast<const unsigned long long *>(skip_pinned);
     unsigned long long skipped = 0, examined = 0;
-    for (int i = 0; i < skip_sample_n; i += 2) { skipped += h[i]; examined += h[i + 1]; }
+    const int n_pairs = skip_sample_n / 2;                                                       // (behind the pairs' counters: the workgroups')
+    for (int i = 0; i < n_pairs; i += 2) { skipped += h[i]; examined += h[i + 1]; }
     if (examined && skipped * COAL_SKIP_MIN_SHARE < examined) skip_pause = COAL_SKIP_PAUSE;
+    unsigned long long left = 0, launched = 0;
+    for (int i = n_pairs; i < skip_sample_n; i += 2) { left += h[i]; launched += h[i + 1]; }
+    if (launched && left * 100 < launched * COAL_EXIT_MIN_PERCENT) exit_pause = COAL_EXIT_PAUSE;          // (a launch in round 8's form counts no workgroups)
   }
   bool coal_bound_armed = false;             // step_async's own hskpng_vterm has just left the maxima: the FIRST coalescence substep may use them
   int last_coal_skip = 0;                    // ("raw_coal_skip": the coalescence launches of the last step_async that used a bound)
@@ -1752,21 +1766,30 @@ struct Particles : IParticles {
       const dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));
       last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
       coal_skip_args<T> ska{};
+      bool exits = false;
       if (bound_armed && !n_max_stale) {
         const bool counted = dbg2(LCX_DBG2_COAL_SKIP_COUNT);
-        if (!counted) { coal_skip_sample.alloc(64); HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 64 * sizeof(unsigned long long), st)); }
-        ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p};
+        if (!counted) { coal_skip_sample.alloc(128); HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 128 * sizeof(unsigned long long), st)); }
+        exits = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
+        if (!exits && exit_pause > 0) --exit_pause;
+        if (exits) ++last_coal_exit;
+        ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p,
+                                counted && exits ? coal_skip_cnt.p + 2 : nullptr};
+        if (counted && !exits) coal_wg_no_exit += gr.x;
         ++last_coal_skip;
       }
       auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
                            deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska);
       };
-      if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true>); else launch(k_coal_ranked<T, false, true>); }
+      // (with a bound: the form whose workgroups leave ahead of the ranking where they keep no pair; LCX_DBG2_NO_COAL_RANK_EXIT, or the last
+      // counters showed too few leaving: round 8's form)
+      if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true>); else launch(k_coal_ranked<T, false, true, true>); }
+      else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true>); else launch(k_coal_ranked<T, false, true>); }
       else if (coal_marks_dead) launch(k_coal_ranked<T, true>); else launch(k_coal_ranked<T, false>);
       if (ska.cmax && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
-        if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 64 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
-        skip_sample_n = ska.cnt ? 2 : 64;
+        if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 128 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
+        skip_sample_n = ska.cnt ? 4 : 128;
         HIPCHK(hipMemcpyAsync(skip_pinned, ska.cnt ? ska.cnt : ska.sample, skip_sample_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(ev_skip, st));
         skip_sample_pending = true;
@@ -2640,8 +2663,9 @@ struct Particles : IParticles {
     const bool rlx_now = opts.rlx && rlx_fires();
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
-    last_coal_ranked = 0; last_coal_skip = 0; coal_bound_armed = false;
-    if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) coal_skip_cnt.alloc_zero(2, st);
+    last_coal_ranked = 0; last_coal_skip = 0; last_coal_exit = 0; coal_bound_armed = false;
+    if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) coal_skip_cnt.alloc_zero(4, st);
+    coal_wg_no_exit = 0;
     vt_fix_pending = false;                           // (a flag of one step_async: nothing of an earlier call is pending)
     last_async_coal = opts.coal != 0;
     coal_marks_dead = n_dims > 0 && nphys > 0 && !opts.rcyc && !src_plain && !rlx_plain && sstp_coal == 1;   // (= the fused move below; with coalescence
@@ -2913,6 +2937,11 @@ struct Particles : IParticles {
       v.assign(1, (unsigned long long)last_coal_skip);
       if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) { if (coal_skip_cnt.p) { auto h = d2h(coal_skip_cnt.p, 2); v.insert(v.end(), h.begin(), h.end()); } else v.insert(v.end(), 2, 0ull); }
     }
+    else if (s == "raw_coal_wg") {                 // LCX_DBG2_COAL_SKIP_COUNT: workgroups of the last step_async's bound launches that left before ranking, and all of them
+      v.assign(2, 0ull);
+      if (dbg2(LCX_DBG2_COAL_SKIP_COUNT) && coal_skip_cnt.p) { auto h = d2h(coal_skip_cnt.p, 4); v[0] = h[2]; v[1] = h[3] + coal_wg_no_exit; }
+    }
+    else if (s == "raw_coal_exit") v.assign(1, (unsigned long long)last_coal_exit);
     else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
@@ -3699,7 +3728,7 @@ struct Particles : IParticles {
       }
       deferred_rs.un = nullptr; last_shuffle_rs.un = nullptr;
       should_now_run_async = should_now_run_cond = selected_before_counting = false;
-      skip_pause = 0; skip_sample_pending = false; rank_pending = false;
+      skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false;
       sync();
     } catch (...) { roll_back(); throw; }
   }

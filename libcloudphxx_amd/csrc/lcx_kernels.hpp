@@ -2547,62 +2547,84 @@ template <class T> struct coal_skip_args {       // what the kernel is handed (c
   unsigned long long *cnt;                       // LCX_DBG2_COAL_SKIP_COUNT only: {pairs skipped, pairs examined}, one atomic each per wave
   unsigned long long *sample;                    // else: 32 such pairs of counters, fed by every 64th workgroup -- what the host decides from whether the
                                                  // bound is worth its maxima (lcx_core.hip poll_skip_sample: a drizzle box at dt = 1 skips 0.2 % of its pairs)
+  unsigned long long *wg;                        // the EXIT form, LCX_DBG2_COAL_SKIP_COUNT: {workgroups that left before ranking, workgroups launched}, one atomic
+                                                 // each per workgroup; else sample + 64 takes 32 such pairs from every 64th workgroup (poll_skip_sample: the
+                                                 // exit pays only where workgroups do leave)
 };
 template <class T> struct coal_skip {            // what a lane has fetched of it ahead of the ranking, for the cells of its positions p0 and p0 + 1
   uint32_t r0, v0, r1, v1; T dv0, dv1, n_max, r_max; const T *emax; int n_emax; unsigned long long *cnt;
 };
+// coal_pair in three pieces, each inlined (k_coal and the ranked kernel without the early exit compile to what they were): which pair the lane
+// owns, the bound's test, and the pair itself from its gathers on.  The first two read no id, so that k_coal_ranked<.., SKIP, EXIT> can run them
+// ahead of its ranking.
+struct coal_own {
+  size_t p;                                            // the position of the pair's first member
+  uint32_t ca, off, end;                               // its cell and the cell's CSR bounds
+  bool second, shift;                                  // the cell is c1, not c0; the members are (i1, i2), not (i0, i1)
+};
+template <class T>
+__device__ __forceinline__ bool
+coal_owned(coal_own &o, const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2,
+           const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1, T *col)
+{
+  o.p = p0; o.ca = c0; o.off = off0; o.end = end0; o.second = false; o.shift = false;
+  const bool even0 = ((uint32_t(o.p) - o.off) & 1u) == 0;
+  if (!(even0 && c1 == o.ca)) {
+    if (even0 && col) col[o.p] = T(0);                 // last SD of a cell with an odd count: no partner
+    o.p = p0 + 1;
+    if (!has2) return false;
+    if (c1 != o.ca) { o.ca = c1; o.off = off1; o.end = end1; o.second = true; }
+    if ((uint32_t(o.p) - o.off) & 1u) return false;    // odd offset: this SD is the b of the previous lane's pair
+    if (c2 != o.ca) { if (col) col[o.p] = T(0); return false; }
+    o.shift = true;
+  }
+  return true;
+}
+template <class T>
+__device__ __forceinline__ T coal_scale(const coal_own &o)
+{
+  const n_t nn = o.end - o.off;
+  return nn > 1 ? (T(nn * (nn - 1)) / 2) / (nn / 2) : T(0);                    // scale_factor, coal.ipp:99-107
+}
+// whether the pair's random number rules the collision out; every lane that owns a pair calls it (the counters are per wave)
+template <class T>
+__device__ __forceinline__ bool
+coal_skipped(const coal_own &o, const T scl, const T dt, const u01_src<T> &rs, const coal_skip<T> *sk, T &u_pre, T &dvc_pre)
+{
+  const T rm = T(__uint_as_float(o.second ? sk->r1 : sk->r0)), vm = T(__uint_as_float(o.second ? sk->v1 : sk->v0));
+  dvc_pre = o.second ? sk->dv1 : sk->dv0;
+  T bound = T(__uint_as_float(CMAX_POISON));                                   // NaN
+  const T r_um = sqrt(rm) * T(1e6) * T(1 + 1. / 1024);
+  if (r_um < sk->r_max - T(11) && vm < T(3e38)) {                              // (false for a NaN)
+    const n_t x0 = r_um >= T(100) ? n_t(floor(r_um / 10) * 10) : n_t(floor(r_um));
+    const int ie = kernel_index(x0);
+    bound = dt / dvc_pre * scl * sk->n_max * T(cst<T>::pi * 4) * rm * vm * sk->emax[ie < sk->n_emax ? ie : sk->n_emax - 1] * T(1 + 1. / 1024);
+    if (bound < T(1e-30)) bound = T(1e-30);
+  }
+  u_pre = philox::u01<T>(o.p, rs.call, rs.seed);
+  const bool skip = bound < T(1) && u_pre >= bound;
+  if (sk->cnt) {
+    const unsigned long long here = __ballot(1), skipped = __ballot(skip);
+    if (int(lane_id()) == __ffsll((long long)here) - 1) { atomicAdd(sk->cnt, (unsigned long long)__popcll(skipped)); atomicAdd(sk->cnt + 1, (unsigned long long)__popcll(here)); }
+  }
+  return skip;
+}
+// the pair itself, from its gathers on.  pre: u and the cell's volume are coal_skipped's (u_pre, dvc_pre)
 template <class T, bool ONISHI>
 __device__ __forceinline__ void
-coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t i0, const uint32_t i1, const uint32_t i2,
-          const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1,
-          n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
-          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_skip<T> *sk = nullptr)
+coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl, const bool pre, const T u_pre, const T dvc_pre,
+             n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
+             const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
 {
-  size_t p = p0;
-  uint32_t ca = c0, off = off0, end = end0, a = i0, b = i1;
-  bool second = false;                                 // (the pair's cell is c1, not c0)
-  {
-    const bool even0 = ((uint32_t(p) - off) & 1u) == 0;
-    if (!(even0 && c1 == ca)) {
-      if (even0 && col) col[p] = T(0);                 // last SD of a cell with an odd count: no partner
-      p = p0 + 1;
-      if (!has2) return;
-      if (c1 != ca) { ca = c1; off = off1; end = end1; second = true; }
-      if ((uint32_t(p) - off) & 1u) return;            // odd offset: this SD is the b of the previous lane's pair
-      if (c2 != ca) { if (col) col[p] = T(0); return; }
-      a = i1; b = i2;
-    }
-  }
-  const uint32_t cnt = end - off;
-  const n_t nn = cnt;
-  const T scl = nn > 1 ? (T(nn * (nn - 1)) / 2) / (nn / 2) : T(0);           // scale_factor, coal.ipp:99-107
-  T u_pre = T(0), dvc_pre = T(0);
-  if (sk) {
-    const T rm = T(__uint_as_float(second ? sk->r1 : sk->r0)), vm = T(__uint_as_float(second ? sk->v1 : sk->v0));
-    dvc_pre = second ? sk->dv1 : sk->dv0;
-    T bound = T(__uint_as_float(CMAX_POISON));                                 // NaN
-    const T r_um = sqrt(rm) * T(1e6) * T(1 + 1. / 1024);
-    if (r_um < sk->r_max - T(11) && vm < T(3e38)) {                            // (false for a NaN)
-      const n_t x0 = r_um >= T(100) ? n_t(floor(r_um / 10) * 10) : n_t(floor(r_um));
-      const int ie = kernel_index(x0);
-      bound = dt / dvc_pre * scl * sk->n_max * T(cst<T>::pi * 4) * rm * vm * sk->emax[ie < sk->n_emax ? ie : sk->n_emax - 1] * T(1 + 1. / 1024);
-      if (bound < T(1e-30)) bound = T(1e-30);
-    }
-    u_pre = philox::u01<T>(p, rs.call, rs.seed);
-    const bool skip = bound < T(1) && u_pre >= bound;
-    if (sk->cnt) {
-      const unsigned long long here = __ballot(1), skipped = __ballot(skip);
-      if (int(lane_id()) == __ffsll((long long)here) - 1) { atomicAdd(sk->cnt, (unsigned long long)__popcll(skipped)); atomicAdd(sk->cnt + 1, (unsigned long long)__popcll(here)); }
-    }
-    if (skip) return;
-  }
+  const size_t p = o.p;
+  const uint32_t ca = o.ca;
   n_t na = n[a], nb = n[b];
-  T rw2a = rw2[a], rw2b = rw2[b], vta = vt[a], vtb = vt[b], dvc = sk ? dvc_pre : dv[ca];
+  T rw2a = rw2[a], rw2b = rw2[b], vta = vt[a], vtb = vt[b], dvc = pre ? dvc_pre : dv[ca];
   asm volatile("" : "+v"(rw2a), "+v"(rw2b), "+v"(vta), "+v"(vtb), "+v"(dvc), "+v"(na), "+v"(nb));   // (one batch, not a chain)
   const T prob = dt / dvc * scl * kernel_calc<T, ONISHI>(kc, na, nb, rw2a, rw2b, vta, vtb, ca);
   n_t col_no = n_t(prob);
   if (pure_const_multi && col_no >= 1) *increase_sstp_coal = 1;
-  const T u = sk ? u_pre : rs.arr ? rs.arr[p] : philox::u01<T>(p, rs.call, rs.seed);
+  const T u = pre ? u_pre : rs.arr ? rs.arr[p] : philox::u01<T>(p, rs.call, rs.seed);
   if (u < prob - col_no) ++col_no;
   if (col_no == 0) { if (col) { col[p] = T(0); col[p + 1] = T(0); } return; }
   if (na >= nb) {                                                            // collide<>, coal.ipp:110-143
@@ -2630,6 +2652,37 @@ coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1
     if (col) col[p + 1] = T(-1);
   }
   if (col) col[p] = T(col_no);
+}
+template <class T, bool ONISHI>
+__device__ __forceinline__ void
+coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t i0, const uint32_t i1, const uint32_t i2,
+          const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1,
+          n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
+          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_skip<T> *sk = nullptr)
+{
+  coal_own o;
+  if (!coal_owned<T>(o, p0, has2, c0, c1, c2, off0, end0, off1, end1, col)) return;
+  const T scl = coal_scale<T>(o);
+  T u_pre = T(0), dvc_pre = T(0);
+  if (sk && coal_skipped<T>(o, scl, dt, rs, sk, u_pre, dvc_pre)) return;
+  coal_collide<T, ONISHI>(o, o.shift ? i1 : i0, o.shift ? i2 : i1, scl, sk != nullptr, u_pre, dvc_pre, n, rw2, vt, rd3, col, dv, dt, kc, rs,
+                          pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark);
+}
+// what a lane of k_coal_ranked<.., SKIP> fetches of the bound for the cells of its positions p0 and p0 + 1
+template <class T>
+__device__ __forceinline__ void
+coal_skip_fetch(coal_skip<T> &sk, const bool pair_lane, const uint32_t c0, const uint32_t c1, const T *dv, const T r_max, const T *emax_l, const coal_skip_args<T> &ska)
+{
+  struct alignas(8) pairU { uint32_t a, b; };
+  pairU m0{CMAX_POISON, CMAX_POISON}, m1{CMAX_POISON, CMAX_POISON};
+  sk.dv0 = sk.dv1 = T(1);
+  if (pair_lane) {
+    m0 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c0)); m1 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c1));
+    sk.dv0 = dv[c0]; sk.dv1 = dv[c1];
+  }
+  sk.r0 = m0.a; sk.v0 = m0.b; sk.r1 = m1.a; sk.v1 = m1.b;
+  sk.n_max = T(*ska.n_max); sk.r_max = r_max; sk.emax = emax_l; sk.n_emax = ska.n_emax;
+  sk.cnt = ska.cnt ? ska.cnt : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
 }
 template <class T, bool ONISHI, bool TAB = false>
 __global__ void __launch_bounds__(BS)
@@ -2665,8 +2718,18 @@ constexpr int COAL_RANKED_POS = 2 * BS;
 // MARK: used-up super-droplets are marked in ijk (the step ends in the fused move), as in k_coal<T, false, true>
 // SKIP: coal_pair's probability bound (above coal_pair); the table of efficiency maxima is copied to LDS ahead of the ranking's first barrier and the
 // per-cell maxima are fetched with the cells' bounds, so that behind the ranking a lane has one LDS read and arithmetic ahead of its gathers
+// EXIT (round 9, with SKIP): the bound's test reads no id -- a pair's position, its cell and the cell's numbers are all it takes -- so every lane
+// runs it AHEAD of the ranking, before any id of the window is loaded, and the workgroup votes (__syncthreads_or): where no pair is kept,
+// nobody would read the order and the workgroup leaves (uniformly), having read 4 B per position and its cells' numbers.  In a cloud without
+// drizzle that is more than nine workgroups in ten.  The others load the window's ids and rank exactly as without EXIT, and only the lanes that
+// kept a pair go on to its gathers: the same random number by position, the same pairs, the same bits.  The test needs the table of efficiency
+// maxima before the ranking's first barrier has published it: a barrier of its own AHEAD OF THE VOTE does (the copy's load is issued with the
+// first level of loads and the test waits for the second anyway; reading the table from global memory instead would put a third dependent
+// load on the path of every workgroup).  A workgroup that ranks pays for that barrier, the vote, and its id loads one level later: the host
+// launches this form only while workgroups do leave (lcx_core.hip poll_skip_sample, COAL_EXIT_MIN_PERCENT).
+// The counters mean what they meant: every lane that owns a pair counts it, skipped or not, ahead of the exit.
 constexpr int EMAX_CAP = 256;
-template <class T, bool MARK, bool SKIP = false>
+template <class T, bool MARK, bool SKIP = false, bool EXIT = false>
 __global__ void __launch_bounds__(BS)
 k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
               n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {})
@@ -2682,14 +2745,38 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   __shared__ T emax_l[SKIP ? EMAX_CAP : 1];
   kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
   if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
+  static_assert(SKIP || !EXIT, "the exit is the bound's");
   const size_t P0 = size_t(blockIdx.x) * OWN;
-  if (P0 + 1 >= n_part) return;                        // (uniform)
   const uint32_t t = threadIdx.x;
+  [[maybe_unused]] unsigned long long *wgc = nullptr;
+  if constexpr (EXIT) {
+    wgc = ska.wg ? ska.wg : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 64 + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
+    if (wgc && t == 0) atomicAdd(wgc + 1, 1ull);
+  }
+  if (P0 + 1 >= n_part) return;                        // (uniform)
   const size_t p0 = P0 + 2 * t;
   const bool pair_lane = p0 + 1 < n_part, has2 = p0 + 2 < n_part;
   // what coal_pair needs of the cells, fetched up front as in k_coal
   uint32_t c0 = 0, c1 = 0, c2 = DEAD_CELL, off0 = 0, end0 = 0, off1 = 0, end1 = 0;
   if (pair_lane) { c0 = sorted_ijk[p0]; c1 = sorted_ijk[p0 + 1]; if (has2) c2 = sorted_ijk[p0 + 2]; }
+  [[maybe_unused]] coal_skip<T> sk;
+  [[maybe_unused]] coal_own own;
+  [[maybe_unused]] bool kept = false;
+  [[maybe_unused]] T scl = T(0), u_pre = T(0), dvc_pre = T(0);
+  if constexpr (EXIT) {
+    if (int(t) < ska.n_emax) emax_l[t] = ska.emax[t];             // (n_emax <= EMAX_CAP = BS: the host launches this form only then)
+    if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
+    coal_skip_fetch<T>(sk, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
+    __syncthreads();                                              // (emax_l)
+    if (pair_lane && coal_owned<T>(own, p0, has2, c0, c1, c2, off0, end0, off1, end1, (T *)nullptr)) {
+      scl = coal_scale<T>(own);
+      kept = !coal_skipped<T>(own, scl, dt, rs, &sk, u_pre, dvc_pre);
+    }
+    if (!__syncthreads_or(kept)) {                                // (uniform: nobody of this workgroup would read the order)
+      if (wgc && t == 0) atomicAdd(wgc, 1ull);
+      return;
+    }
+  }
   const size_t last = (P0 + OWN < n_part ? P0 + OWN + 1 : n_part) - 1;       // the last position whose id a lane of this workgroup may need
   // the four entries of the window
   const size_t q1 = P0 + t, q2 = P0 + BS + t, q3 = P0 + 2 * BS + t;
@@ -2701,19 +2788,9 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if (in1) { const uint32_t c = sorted_ijk[q1]; id1 = in[q1]; s1 = cell_start[c]; e1 = cell_start[c + 1]; }
   if (in2) { const uint32_t c = sorted_ijk[q2]; id2 = in[q2]; s2 = cell_start[c]; e2 = cell_start[c + 1]; }
   if (t == WAVE) { const uint32_t c = sorted_ijk[last]; bounds[1] = cell_start[c + 1]; bounds[3] = cell_start[c]; }   // (a wave that does not also hold lane 0)
-  if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
-  [[maybe_unused]] coal_skip<T> sk;
-  if constexpr (SKIP) {
-    struct alignas(8) pairU { uint32_t a, b; };
-    pairU m0{CMAX_POISON, CMAX_POISON}, m1{CMAX_POISON, CMAX_POISON};
-    sk.dv0 = sk.dv1 = T(1);
-    if (pair_lane) {
-      m0 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c0)); m1 = *reinterpret_cast<const pairU *>(ska.cmax + 2 * size_t(c1));
-      sk.dv0 = dv[c0]; sk.dv1 = dv[c1];
-    }
-    sk.r0 = m0.a; sk.v0 = m0.b; sk.r1 = m1.a; sk.v1 = m1.b;
-    sk.n_max = T(*ska.n_max); sk.r_max = kc.r_max; sk.emax = emax_l; sk.n_emax = ska.n_emax;
-    sk.cnt = ska.cnt ? ska.cnt : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
+  if constexpr (!EXIT) if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
+  if constexpr (SKIP && !EXIT) {
+    coal_skip_fetch<T>(sk, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
     if (int(t) < ska.n_emax) emax_l[t] = ska.emax[t];           // (n_emax <= EMAX_CAP = BS: the host launches this form only then)
   }
 #pragma unroll
@@ -2771,6 +2848,13 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
     }
   }
   __syncthreads();
+  if constexpr (EXIT) {
+    if (!kept) return;
+    const uint32_t s = own.shift ? 1u : 0u;
+    coal_collide<T, false>(own, ids[2 * t + s], ids[2 * t + s + 1], scl, true, u_pre, dvc_pre, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr,
+                           (T *)nullptr, (T *)nullptr, ijk_mark);
+    return;
+  }
   if (!pair_lane) return;
   const uint32_t i0 = ids[2 * t], i1 = ids[2 * t + 1], i2 = has2 ? ids[2 * t + 2] : 0u;
   coal_pair<T, false>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,

@@ -129,6 +129,8 @@ class dbg(enum.IntFlag):
 class dbg2(enum.IntFlag):
     """opts_init.dbg_flags2 (include/lcx.h, enum lcx_dbg2)"""
     COAL_SKIP_COUNT = 1 << 0
+    NO_COAL_RANK_EXIT = 1 << 1
+    COAL_RANK_EXIT_ALWAYS = 1 << 2
 
 
 class cond_kernel(enum.IntEnum):

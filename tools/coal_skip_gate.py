@@ -3,12 +3,21 @@
 OpenMP oracle on bench.py's fields, with k_geometric and interpolated_efficiency restated in numpy -- and the assertion that the bound is
 one: prob <= bound for every pair.
 
-    python3 tools/coal_skip_gate.py [--n 16] [--workload stratocumulus|coal-stress] [--dt 1] [--steps 5,50,200]
+    python3 tools/coal_skip_gate.py [--n 16] [--sd 64] [--workload stratocumulus|coal-stress] [--dt 1] [--steps 5,50,200] [--group 512] [--mixed] [--sparse K:R]
 
 Two bounds per cell: "table" takes the largest efficiency of the whole table, "radius" the largest one that radii up to the cell's largest
 can reach (what the kernel uses).  A line is 16 consecutive positions of the cell-sorted order, the granularity of the gathers' traffic.
 The pairing is the coalescence's: a random order inside each cell, pairs at even offsets.  For coal-stress the quantiles of the bound and
 the share of pairs that collide are printed as well (what tests/test_hip_coal_skip.py's time steps were chosen from).
+
+For the workgroups that leave ahead of the ranking (k_coal_ranked<.., SKIP, EXIT>) the "radius" row also gives the share of the groups of
+--group consecutive positions (a workgroup's 512) and of the cells that hold at least one kept pair.  --mixed: after init every droplet
+with x < x1 / 2 gets rw2 x 1e-4 and rd3 x 1e-6 -- half of the sorted order that cannot collide next to a half that does
+(tests/test_hip_coal_rank_exit.py; its figures are --workload coal-stress --dt 0.02 --mixed --steps 1,2,5,10 --group 256).  --sparse K:R: every
+droplet shrunk like that except those of the cells with index % K == R, which become 100 um and 50 um drops in turn, and every
+multiplicity 2.5e9 -- in the natural spectrum a kept pair collides once in two thousand times (the bound takes the box's largest
+multiplicity and the cell's largest radius and velocity); here one in six does, so that at K = 8 a group of 512 positions holds ONE cell
+whose one or two kept pairs often collide (the same test file's sparse box: --workload coal-stress --dt 0.05 --sparse 8:2 --steps 1,2,5,10).
 """
 import argparse
 import os
@@ -66,7 +75,7 @@ def float_up(x):
     return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float64)
 
 
-def gate(orc, oi, tab, r_max, emax, rng, label):
+def gate(orc, oi, tab, r_max, emax, rng, label, group=512):
     n, rw2, vt, ijk = orc.state_u64("n").astype(np.float64), orc.get_attr("rw2"), orc.state_real("vt"), orc.state_u64("ijk").astype(np.int64)
     ncell = oi.nx * oi.ny * oi.nz
     dv = oi.dx * oi.dy * oi.dz
@@ -85,7 +94,7 @@ def gate(orc, oi, tab, r_max, emax, rng, label):
     u = rng.random(len(pa))
     rw2_max, vt_max = np.zeros(ncell), np.zeros(ncell)
     np.maximum.at(rw2_max, ijk, float_up(rw2)); np.maximum.at(vt_max, ijk, float_up(vt))
-    assert (vt >= 0).all()
+    assert (vt >= 0).all() and np.isfinite(rw2).all() and np.isfinite(vt).all()
     r_um = np.sqrt(rw2_max) * 1e6 * MARGIN
     x0 = np.where(r_um >= 100, np.floor(r_um / 10) * 10, np.floor(r_um))
     e_radius = np.where(r_um < r_max - 11, emax[np.minimum(kernel_index(x0), len(emax) - 1)], np.nan)
@@ -103,6 +112,14 @@ def gate(orc, oi, tab, r_max, emax, rng, label):
         q = np.nanpercentile(bound, [1, 10, 50, 99])
         print("  %-6s bound: pairs kept %.5f, lines kept %.5f, skipped %.5f; bound quantiles 1 %% %.3g, 10 %% %.3g, median %.3g, 99 %% %.3g; cells with bound < 1: %.3f"
               % (name, kept.mean(), len(lines) / n_lines, skip.mean(), q[0], q[1], q[2], q[3], (bound < 1).mean()))
+        if name == "radius":                                 # a pair belongs to the group of the lane that owns it: position pa or pa - 1, the same group
+            groups = np.unique(pa[kept] // group)
+            print("         groups of %d positions with a kept pair %.4f (%d of %d), cells with a kept pair %.4f, pairs that collide %d"
+                  % (group, len(groups) / ((len(c) + group - 1) // group), len(groups), (len(c) + group - 1) // group,
+                     len(np.unique(cell[kept])) / ncell, int((u < prob).sum())))
+            per_group = np.bincount(pa[kept] // group)
+            print("         kept pairs in a group that has any: mean %.2f, most %d; bound of the kept pairs' cells: median %.3g, below 1: %.3f"
+                  % (per_group[per_group > 0].mean(), per_group.max(), np.median(bound[kept]), (bound[kept] < 1).mean()))
 
 
 def main():
@@ -111,23 +128,46 @@ def main():
     ap.add_argument("--workload", default="stratocumulus", choices=["stratocumulus", "coal-stress"])
     ap.add_argument("--dt", type=float, default=1.)
     ap.add_argument("--steps", default="5,50,200")
+    ap.add_argument("--sd", type=int, default=64)
+    ap.add_argument("--group", type=int, default=512)
+    ap.add_argument("--mixed", action="store_true")
+    ap.add_argument("--sparse", default=None, metavar="K:R")
     args = ap.parse_args()
     at = sorted(int(s) for s in args.steps.split(","))
     n = args.n
-    oi = bench.make_opts_init(n, n, n, 64, 40., 1, 1, 44, args.workload, args.dt)
+    oi = bench.make_opts_init(n, n, n, args.sd, 40., 1, 1, 44, args.workload, args.dt)
     r_max, tab = load_table(oi.kernel)
     emax = efficiency_maxima(tab)
     print("kernel %s: table maximum %.4g, maximum reachable up to 15 um %.4g" % (lgrngn.kernel_t(oi.kernel).name, tab.max(), emax[15]))
     th, rv, rhod, Cx, Cy, Cz = bench.make_fields(n, n, n, 0, n, np, np.float64)
     orc = h.oracle_omp_particles(oi)
     orc.init(th, rv, rhod, Cx=Cx, Cy=Cy, Cz=Cz)
+    if args.mixed:
+        x, rw2, rd3 = orc.get_attr("x"), orc.get_attr("rw2"), orc.get_attr("rd3")
+        low = x < 0.5 * oi.x1
+        rw2[low] *= 1e-4; rd3[low] *= 1e-6
+        orc.set_particles(orc.state_u64("n"), rd3, rw2, orc.get_attr("kappa"), orc.state_real("vt"), x, orc.get_attr("y"), orc.get_attr("z"))
+    if args.sparse:
+        K, R = (int(v) for v in args.sparse.split(":"))
+        x, y, z, rw2, rd3 = orc.get_attr("x"), orc.get_attr("y"), orc.get_attr("z"), orc.get_attr("rw2"), orc.get_attr("rd3")
+        cell = ((x // oi.dx).astype(np.int64) * oi.ny + (y // oi.dy).astype(np.int64)) * oi.nz + (z // oi.dz).astype(np.int64)
+        low = cell % K != R
+        big = np.nonzero(~low)[0]
+        print("sparse: %d droplets in %d cells become drops" % (len(big), len(np.unique(cell[big]))))
+        rw2[low] *= 1e-4; rd3[low] *= 1e-6
+        rw2[big[0::2]], rw2[big[1::2]], rd3[big] = 100e-6 ** 2, 50e-6 ** 2, 1e-6 ** 3
+        orc.set_particles(np.full(len(x), 25 * 10 ** 8, dtype=np.uint64), rd3, rw2, orc.get_attr("kappa"), orc.state_real("vt"), x, y, z)
     opts = lgrngn.opts_t()
     rng = np.random.default_rng(7)
     for step in range(1, at[-1] + 1):
         orc.step_sync(opts, th, rv, rhod, Cx, Cy, Cz)
         if step in at:                                       # what this step's coalescence will see: the droplets behind condensation, velocities fresh
             orc.stage("hskpng_Tpr"); orc.stage("hskpng_vterm_all")
-            gate(orc, oi, tab, r_max, emax, rng, "step %d" % step)
+            if args.sparse and step == at[0]:                # (the cell index restated above is the library's)
+                x, y, z = orc.get_attr("x"), orc.get_attr("y"), orc.get_attr("z")
+                mine = ((x // oi.dx).astype(np.int64) * oi.ny + (y // oi.dy).astype(np.int64)) * oi.nz + (z // oi.dz).astype(np.int64)
+                assert np.array_equal(mine, orc.state_u64("ijk").astype(np.int64))
+            gate(orc, oi, tab, r_max, emax, rng, "step %d" % step, args.group)
         orc.step_async(opts)
 
 
