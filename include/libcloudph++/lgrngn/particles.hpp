@@ -17,6 +17,7 @@
 #include "../../lcx_chem.h"
 #include "../../lcx_state.h"
 #include "../../lcx_diag.h"
+#include "../../lcx_coal_rates.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -105,6 +106,14 @@ namespace libcloudphxx { namespace lgrngn {
     diag_req_t &dry_mom(int k_) { count = LCX_DIAG_DRY_MOM; k = k_; return *this; }
     diag_req_t &wet_mom(int k_) { count = LCX_DIAG_WET_MOM; k = k_; return *this; }
     diag_req_t &kappa_mom(int k_) { count = LCX_DIAG_KAPPA_MOM; k = k_; return *this; }
+  };
+
+  // the accumulators of particles_t<real_t, HIP>::coal_rates (an extension without a reference counterpart; include/lcx_coal_rates.h
+  // defines each of them)
+  enum class coal_rate_t : int
+  {
+    acnv_m3 = LCX_CR_ACNV_M3, acnv_nc = LCX_CR_ACNV_NC, acnv_nr = LCX_CR_ACNV_NR, accr_m3 = LCX_CR_ACCR_M3, accr_nc = LCX_CR_ACCR_NC,
+    self_cloud_n = LCX_CR_SELF_CLOUD_N, self_rain_n = LCX_CR_SELF_RAIN_N, count = LCX_CR_COUNT
   };
 
   namespace detail
@@ -349,6 +358,21 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_diag_batch_info(pimpl->h, &rpp, scratch_bytes));
       return rpp;
     }
+    // EXTENSION, no reference counterpart (include/lcx_coal_rates.h): per-cell sums of what every collision event moves between cloud
+    // (wet radius below r_thr) and rain -- autoconversion, accretion, self-collection -- filled inside the coalescence kernels while
+    // enabled.  coal_rates: out[int(coal_rate_t) * n_cell + cell] (resized to count * n_cell), the numbers as doubles; reset zeroes the
+    // accumulators behind the read.  diag_coal_rate fills outbuf() like a diag_*_mom call.  A snapshot does not hold them: a restored
+    // object is disabled.  Not virtual: particles_proto_t stays the reference's.
+    void coal_rates_enable(real_t r_thr) { detail::lcx_check(lcx_coal_rates_enable(pimpl->h, double(r_thr))); }
+    void coal_rates_disable() { detail::lcx_check(lcx_coal_rates_disable(pimpl->h)); }
+    void coal_rates(std::vector<double> &out, bool reset = false)
+    {
+      size_t n_cell = 0;
+      detail::lcx_check(lcx_n_cell(pimpl->h, &n_cell));
+      out.resize(size_t(LCX_CR_COUNT) * n_cell);
+      detail::lcx_check(lcx_coal_rates_read(pimpl->h, out.data(), n_cell, 0, reset ? 1 : 0));
+    }
+    void diag_coal_rate(coal_rate_t which) { detail::lcx_check(lcx_diag_coal_rate(pimpl->h, int(which))); }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

@@ -27,6 +27,7 @@
 #include "../../include/lcx_chem.h"
 #include "../../include/lcx_state.h"
 #include "../../include/lcx_diag.h"
+#include "../../include/lcx_coal_rates.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -135,6 +136,13 @@ struct IParticles {
   // many selections and moments in one pass (include/lcx_diag.h); the list has been validated
   virtual void diag_batch(const lcx_diag_req_t *, int, void *, size_t, bool) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
   virtual void diag_batch_info(int *, size_t *) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
+  // collision rates per cell (include/lcx_coal_rates.h): built for a single-device object
+  [[noreturn]] static void no_coal_rates() { throw std::runtime_error("libcloudph++: coal_rates on a multi-device object is not built"); }
+  virtual void coal_rates_enable(double) { no_coal_rates(); }
+  virtual void coal_rates_disable() { no_coal_rates(); }
+  virtual void coal_rates_info(int *, double *, unsigned long long *) { no_coal_rates(); }
+  virtual void coal_rates_read(double *, size_t, bool, bool) { no_coal_rates(); }
+  virtual void diag_coal_rate(int) { no_coal_rates(); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -1731,6 +1739,59 @@ struct Particles : IParticles {
     return !dbg(LCX_DBG_NO_COAL_SKIP) && n_emax > 0 && nphys > 0 && (vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST) &&
            !sort_deferred && (coal_ranks_owed_order() || coal_owes_unshuffled_cells());
   }
+  // ---- collision rates per cell (include/lcx_coal_rates.h): seven accumulators per cell, fed by the coalescence kernels' TALLY forms ----
+  // While they are on, every coalescence launch is the TALLY form of the kernel it would have been (bound, early exit and all: a skipped pair is
+  // one that cannot collide); off, nothing below is looked at and every launch is the one it was.
+  bool cr_on = false; double cr_r_thr = 0; unsigned long long cr_launches = 0;
+  DevBuf<unsigned long long> cr_acc; DevBuf<double> cr_out; std::vector<double> cr_host;
+  static constexpr unsigned CR_M3_ROWS = (1u << LCX_CR_ACNV_M3) | (1u << LCX_CR_ACCR_M3);
+  coal_tally_arg<T, true> cr_arg()                  // what a tallying launch is handed; counts the launch ("launches" of lcx_coal_rates_info)
+  {
+    double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, cr_r_thr, cr_r_thr, lo, hi);       // (what lcx_diag_wet_rng(r_thr, ...) selects from)
+    ++cr_launches;
+    return coal_tally_arg<T, true>{cr_acc.p, ncell, T(lo)};
+  }
+  void cr_zero() { HIPCHK(hipMemsetAsync(cr_acc.p, 0, size_t(LCX_CR_COUNT) * ncell * sizeof(unsigned long long), st)); cr_launches = 0; }
+  void coal_rates_enable(double r_thr) override
+  {
+    if (!(r_thr > 0) || !std::isfinite(r_thr)) throw lcx_error("libcloudph++: coal_rates: r_thr must be positive and finite");
+    cr_acc.alloc(size_t(LCX_CR_COUNT) * ncell);
+    cr_r_thr = r_thr; cr_on = true;
+    cr_zero();
+  }
+  void coal_rates_disable() override { cr_on = false; cr_r_thr = 0; cr_launches = 0; if (cr_acc.p) { HIPCHK(hipStreamSynchronize(st)); cr_acc.release(); cr_out.release(); } }
+  void coal_rates_info(int *enabled, double *r_thr, unsigned long long *launches) override
+  {
+    if (enabled) *enabled = cr_on ? 1 : 0;
+    if (r_thr) *r_thr = cr_r_thr;
+    if (launches) *launches = cr_launches;
+  }
+  void cr_need(const char *what) const { if (!cr_on) throw lcx_error(std::string("libcloudph++: coal_rates: ") + what + " while the accumulators are not enabled (lcx_coal_rates_enable)"); }
+  void coal_rates_read(double *out, size_t stride, bool on_device, bool reset) override
+  {
+    cr_need("read");
+    if (!out) throw lcx_error("libcloudph++: coal_rates: out == NULL");
+    if (stride < ncell) throw lcx_error("libcloudph++: coal_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
+    const dim3 gr(nblk(ncell), LCX_CR_COUNT);
+    if (on_device) hipLaunchKernelGGL(k_coal_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cr_acc.p, CR_M3_ROWS, out, stride);
+    else {
+      cr_out.alloc(size_t(LCX_CR_COUNT) * ncell); cr_host.resize(size_t(LCX_CR_COUNT) * ncell);
+      hipLaunchKernelGGL(k_coal_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cr_acc.p, CR_M3_ROWS, cr_out.p, ncell);
+      HIPCHK(hipMemcpyAsync(cr_host.data(), cr_out.p, cr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (reset) cr_zero();
+    sync();
+    if (!on_device) for (int w = 0; w < LCX_CR_COUNT; ++w) memcpy(out + size_t(w) * stride, cr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
+  }
+  void diag_coal_rate(int which) override
+  {
+    cr_need("diag_coal_rate");
+    if (!init_called) throw lcx_error("libcloudph++: coal_rates: diag_coal_rate before init()");
+    if (which < 0 || which >= LCX_CR_COUNT) throw lcx_error("libcloudph++: coal_rates: which = " + std::to_string(which) + " is outside 0 .. " + std::to_string(LCX_CR_COUNT - 1));
+    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(cr_acc.p + size_t(which) * ncell),
+                       int((CR_M3_ROWS >> which) & 1u), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
+    sync();
+  }
   void refresh_n_max()
   {
     if (!n_max_stale) return;
@@ -1778,15 +1839,21 @@ struct Particles : IParticles {
         if (counted && !exits) coal_wg_no_exit += gr.x;
         ++last_coal_skip;
       }
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
-                           deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska);
-      };
       // (with a bound: the form whose workgroups leave ahead of the ranking where they keep no pair; LCX_DBG2_NO_COAL_RANK_EXIT, or the last
-      // counters showed too few leaving: round 8's form)
-      if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true>); else launch(k_coal_ranked<T, false, true, true>); }
-      else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true>); else launch(k_coal_ranked<T, false, true>); }
-      else if (coal_marks_dead) launch(k_coal_ranked<T, true>); else launch(k_coal_ranked<T, false>);
+      // counters showed too few leaving: round 8's form.  With the collision rates on: the same form, tallying)
+      auto launch_all = [&](auto tallies) {
+        constexpr bool TL = decltype(tallies)::value;
+        coal_tally_arg<T, TL> ta{};
+        if constexpr (TL) ta = cr_arg();
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
+                             deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
+        };
+        if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL>); else launch(k_coal_ranked<T, false, true, true, TL>); }
+        else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, false, TL>); else launch(k_coal_ranked<T, false, true, false, TL>); }
+        else if (coal_marks_dead) launch(k_coal_ranked<T, true, false, false, TL>); else launch(k_coal_ranked<T, false, false, false, TL>);
+      };
+      if (cr_on) launch_all(std::true_type{}); else launch_all(std::false_type{});
       if (ska.cmax && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
         if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 128 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
         skip_sample_n = ska.cnt ? 4 : 128;
@@ -1803,12 +1870,24 @@ struct Particles : IParticles {
     auto launch = [&](auto kern, bool need_col = true) {
       hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
                          A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
-                         ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr);
+                         ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr, coal_tally_arg<T, false>{});
     };
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
-    if (onishi) { last_coal_kernel = 1; launch(k_coal<T, true>); }
+    const bool production = tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead;
+    if (cr_on) {                                        // the same three kernels, feeding the collision rates' accumulators
+      const coal_tally_arg<T, true> ta = cr_arg();
+      auto tally = [&](auto kern, bool need_col = true) {
+        hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
+                           A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
+                           ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr, ta);
+      };
+      if (onishi) { last_coal_kernel = 1; tally(k_coal<T, true, false, true>); }
+      else if (production) { last_coal_kernel = 2; tally(k_coal<T, false, true, true>, kappa_pass || chem_pass); }
+      else { last_coal_kernel = 0; tally(k_coal<T, false, false, true>); }
+    }
+    else if (onishi) { last_coal_kernel = 1; launch(k_coal<T, true>); }
     // (the production kernel writes the collision record only for the kappa pass: nothing else reads it outside a replayed run)
-    else if (tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead) { last_coal_kernel = 2; launch(k_coal<T, false, true>, kappa_pass || chem_pass); }
+    else if (production) { last_coal_kernel = 2; launch(k_coal<T, false, true>, kappa_pass || chem_pass); }
     else { last_coal_kernel = 0; launch(k_coal<T, false>); }
     if (kappa_pass)
       hipLaunchKernelGGL(k_coal_kappa<T>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sid(), col.p, A.kpa.p, A.rd3.p);
@@ -3730,6 +3809,7 @@ struct Particles : IParticles {
       should_now_run_async = should_now_run_cond = selected_before_counting = false;
       skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false;
       sync();
+      coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
     } catch (...) { roll_back(); throw; }
   }
   // what the constructor left zero and a load that failed half-way may have written
@@ -4001,6 +4081,14 @@ int lcx_diag_batch(lcx_particles *h, const lcx_diag_req_t *req, int n_req, void 
   if (n_req == 0) return 0;
   LCX_TRY(H->diag_batch(req, n_req, out, req_stride, out_on_device != 0))
 }
+
+// ---- collision rates per cell (include/lcx_coal_rates.h) ----
+int lcx_coal_rates_enable(lcx_particles *h, double r_thr) { LCX_TRY(H->coal_rates_enable(r_thr)) }
+int lcx_coal_rates_disable(lcx_particles *h) { LCX_TRY(H->coal_rates_disable()) }
+int lcx_coal_rates_info(lcx_particles *h, int *enabled, double *r_thr, unsigned long long *launches) { LCX_TRY(H->coal_rates_info(enabled, r_thr, launches)) }
+int lcx_coal_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
+{ LCX_TRY(H->coal_rates_read(out, stride, out_on_device != 0, reset != 0)) }
+int lcx_diag_coal_rate(lcx_particles *h, int which) { LCX_TRY(H->diag_coal_rate(which)) }
 
 // ---- checkpoint and restart (include/lcx_state.h) ----
 int lcx_snapshot_size(lcx_particles *h, size_t *bytes) { LCX_TRY(*bytes = H->snapshot_size()) }

@@ -2609,12 +2609,39 @@ coal_skipped(const coal_own &o, const T scl, const T dt, const u01_src<T> &rs, c
   }
   return skip;
 }
+// Collision rates (include/lcx_coal_rates.h): what an event moves between cloud (rw2 < lo) and rain (rw2 >= lo), added to
+// seven accumulators of the pair's cell.  acc is [LCX_CR_COUNT][n_cell] words of 8 bytes: the two M3 rows hold doubles, the five number rows
+// unsigned 64-bit integers.  D is the member with the larger or equal multiplicity (the donor: col_no * m of its droplets vanish), R the other (the
+// receiver: its m droplets become droplets of the radius that the kernel stores, rw2_new, and the product's class is read from that stored value).
+// One atomic per event and accumulator that the event's row names: the integer sums do not depend on the order, the M3 sums do in their last bits.
+// A rain member's product counts as rain (it is no smaller than the member).
+template <class T, bool TALLY> struct coal_tally_arg {};                          // TALLY == false: nothing travels and nothing is compiled
+template <class T> struct coal_tally_arg<T, true> { unsigned long long *acc; size_t n_cell; T lo; };
+template <class T>
+__device__ __forceinline__ void
+coal_tally_event(const coal_tally_arg<T, true> &ta, const uint32_t cell, const n_t col_no, const n_t m, const T rw2D, const T rw2R, const T rw2_new)
+{
+  if (m == 0) return;                                                              // (a receiver without droplets moves nothing)
+  unsigned long long *row = ta.acc + cell;
+  auto num = [&](int w, unsigned long long v) { if (v) atomicAdd(row + size_t(w) * ta.n_cell, v); };
+  auto m3 = [&](int w, double v) { unsafeAtomicAdd(reinterpret_cast<double *>(row + size_t(w) * ta.n_cell), v); };
+  auto cube = [](T r2) { const double x = double(r2); return x * sqrt(x); };
+  const bool rainD = !(rw2D < ta.lo), rainR = !(rw2R < ta.lo), rainP = rainD || rainR || !(rw2_new < ta.lo);
+  const unsigned long long cm = (unsigned long long)col_no * m;
+  if (!rainD && !rainR) {
+    if (!rainP) num(LCX_CR_SELF_CLOUD_N, cm);
+    else { m3(LCX_CR_ACNV_M3, double(m) * (double(col_no) * cube(rw2D) + cube(rw2R))); num(LCX_CR_ACNV_NC, cm + m); num(LCX_CR_ACNV_NR, m); }
+  }
+  else if (!rainD) { m3(LCX_CR_ACCR_M3, double(col_no) * double(m) * cube(rw2D)); num(LCX_CR_ACCR_NC, cm); }
+  else if (!rainR) { m3(LCX_CR_ACCR_M3, double(m) * cube(rw2R)); num(LCX_CR_ACCR_NC, m); num(LCX_CR_SELF_RAIN_N, cm - m); }
+  else num(LCX_CR_SELF_RAIN_N, cm);
+}
 // the pair itself, from its gathers on.  pre: u and the cell's volume are coal_skipped's (u_pre, dvc_pre)
-template <class T, bool ONISHI>
+template <class T, bool ONISHI, bool TALLY = false>
 __device__ __forceinline__ void
 coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl, const bool pre, const T u_pre, const T dvc_pre,
              n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
-             const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
+             const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_tally_arg<T, TALLY> &ta = {})
 {
   const size_t p = o.p;
   const uint32_t ca = o.ca;
@@ -2634,6 +2661,7 @@ coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl,
                                                                                // then needs no look at n; the sorted order of this step still holds it)
     const T rw_b = cbrt(col_no * rw2a * sqrt(rw2a) + rw2b * sqrt(rw2b));
     rw2[b] = rw_b * rw_b;
+    if constexpr (TALLY) coal_tally_event<T>(ta, ca, col_no, nb, rw2a, rw2b, rw_b * rw_b);
     rd3[b] = col_no * rd3[a] + rd3[b];
     vt[b] = T(-1);
     if (rc2) rc2[b] = T(-1);                                                 // invalidator, coal.ipp:33-44,527-545
@@ -2645,6 +2673,7 @@ coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl,
     if (ijk_mark && nb == col_no * na) ijk_mark[b] = DEAD_CELL;
     const T rw_a = cbrt(col_no * rw2b * sqrt(rw2b) + rw2a * sqrt(rw2a));
     rw2[a] = rw_a * rw_a;
+    if constexpr (TALLY) coal_tally_event<T>(ta, ca, col_no, na, rw2b, rw2a, rw_a * rw_a);
     rd3[a] = col_no * rd3[b] + rd3[a];
     vt[a] = T(-1);
     if (rc2) rc2[a] = T(-1);
@@ -2653,20 +2682,21 @@ coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl,
   }
   if (col) col[p] = T(col_no);
 }
-template <class T, bool ONISHI>
+template <class T, bool ONISHI, bool TALLY = false>
 __device__ __forceinline__ void
 coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t i0, const uint32_t i1, const uint32_t i2,
           const uint32_t off0, const uint32_t end0, const uint32_t off1, const uint32_t end1,
           n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, const T dt, const coal_kernel_cfg<T> &kc, const u01_src<T> &rs,
-          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_skip<T> *sk = nullptr)
+          const int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, const coal_skip<T> *sk = nullptr,
+          const coal_tally_arg<T, TALLY> &ta = {})
 {
   coal_own o;
   if (!coal_owned<T>(o, p0, has2, c0, c1, c2, off0, end0, off1, end1, col)) return;
   const T scl = coal_scale<T>(o);
   T u_pre = T(0), dvc_pre = T(0);
   if (sk && coal_skipped<T>(o, scl, dt, rs, sk, u_pre, dvc_pre)) return;
-  coal_collide<T, ONISHI>(o, o.shift ? i1 : i0, o.shift ? i2 : i1, scl, sk != nullptr, u_pre, dvc_pre, n, rw2, vt, rd3, col, dv, dt, kc, rs,
-                          pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark);
+  coal_collide<T, ONISHI, TALLY>(o, o.shift ? i1 : i0, o.shift ? i2 : i1, scl, sk != nullptr, u_pre, dvc_pre, n, rw2, vt, rd3, col, dv, dt, kc, rs,
+                                 pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark, ta);
 }
 // what a lane of k_coal_ranked<.., SKIP> fetches of the bound for the cells of its positions p0 and p0 + 1
 template <class T>
@@ -2684,11 +2714,12 @@ coal_skip_fetch(coal_skip<T> &sk, const bool pair_lane, const uint32_t c0, const
   sk.n_max = T(*ska.n_max); sk.r_max = r_max; sk.emax = emax_l; sk.n_emax = ska.n_emax;
   sk.cnt = ska.cnt ? ska.cnt : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
 }
-template <class T, bool ONISHI, bool TAB = false>
+// TALLY: the collision rates' accumulators are fed (coal_tally_event); without it the argument is empty and the kernel is what it was
+template <class T, bool ONISHI, bool TAB = false, bool TALLY = false>
 __global__ void __launch_bounds__(BS)
 k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, const uint32_t *cell_start,
        n_t *n, T *rw2, T *vt, T *rd3, T *col, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs,
-       int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark)
+       int pure_const_multi, int *increase_sstp_coal, T *rc2, T *ict, uint32_t *ijk_mark, coal_tally_arg<T, TALLY> ta = {})
 {
   if (TAB) { kc.kernel = LCX_KERNEL_HALL; pure_const_multi = 0; rs.arr = nullptr; rc2 = nullptr; ict = nullptr; __builtin_assume(ijk_mark != nullptr); }
   const size_t p0 = 2 * gid();
@@ -2700,7 +2731,8 @@ k_coal(size_t n_part, const uint32_t *sorted_id, const uint32_t *sorted_ijk, con
   const uint32_t c0 = sorted_ijk[p0], c1 = sorted_ijk[p0 + 1], c2 = has2 ? sorted_ijk[p0 + 2] : DEAD_CELL;
   const uint32_t i0 = sorted_id[p0], i1 = sorted_id[p0 + 1], i2 = has2 ? sorted_id[p0 + 2] : 0u;
   const uint32_t off0 = cell_start[c0], end0 = cell_start[c0 + 1], off1 = cell_start[c1], end1 = cell_start[c1 + 1];
-  coal_pair<T, ONISHI>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, col, dv, dt, kc, rs, pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark);
+  coal_pair<T, ONISHI, TALLY>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, col, dv, dt, kc, rs, pure_const_multi, increase_sstp_coal, rc2, ict, ijk_mark,
+                              (const coal_skip<T> *)nullptr, ta);
 }
 // Round 7: the production coalescence RANKING EACH CELL'S ORDER FOR ITSELF.  k_cellrank_bkt wrote the shuffled order to memory for this kernel
 // alone to read back (17 B per super-droplet and step).  Here a workgroup owns the 2 BS positions [P0, P0 + 2 BS) of the cell-sorted order as
@@ -2729,10 +2761,12 @@ constexpr int COAL_RANKED_POS = 2 * BS;
 // launches this form only while workgroups do leave (lcx_core.hip poll_skip_sample, COAL_EXIT_MIN_PERCENT).
 // The counters mean what they meant: every lane that owns a pair counts it, skipped or not, ahead of the exit.
 constexpr int EMAX_CAP = 256;
-template <class T, bool MARK, bool SKIP = false, bool EXIT = false>
+// TALLY: as in k_coal, in every form (a pair that the bound skips cannot collide and adds nothing)
+template <class T, bool MARK, bool SKIP = false, bool EXIT = false, bool TALLY = false>
 __global__ void __launch_bounds__(BS)
 k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
-              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {})
+              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {},
+              coal_tally_arg<T, TALLY> ta = {})
 {
   using KEY = uint32_t;
   constexpr int CAP = 4 * BS, OWN = COAL_RANKED_POS;
@@ -2851,14 +2885,14 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if constexpr (EXIT) {
     if (!kept) return;
     const uint32_t s = own.shift ? 1u : 0u;
-    coal_collide<T, false>(own, ids[2 * t + s], ids[2 * t + s + 1], scl, true, u_pre, dvc_pre, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr,
-                           (T *)nullptr, (T *)nullptr, ijk_mark);
+    coal_collide<T, false, TALLY>(own, ids[2 * t + s], ids[2 * t + s + 1], scl, true, u_pre, dvc_pre, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr,
+                                  (T *)nullptr, (T *)nullptr, ijk_mark, ta);
     return;
   }
   if (!pair_lane) return;
   const uint32_t i0 = ids[2 * t], i1 = ids[2 * t + 1], i2 = has2 ? ids[2 * t + 2] : 0u;
-  coal_pair<T, false>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,
-                      (T *)nullptr, ijk_mark, SKIP ? &sk : (const coal_skip<T> *)nullptr);
+  coal_pair<T, false, TALLY>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,
+                             (T *)nullptr, ijk_mark, SKIP ? &sk : (const coal_skip<T> *)nullptr, ta);
 }
 // weighted_summator, coal.ipp:57-97,458-480 (only with more than one kappa in the run)
 template <class T>
@@ -2877,6 +2911,23 @@ __global__ void k_coal_kappa(size_t n_part, const uint32_t *sorted_id, const T *
     else          { ka = (kb * rd3b + ka * rd3_old) / (rd3b + rd3_old); rd3_old += rd3b; }
   }
   if (na_ge_nb) kpa[b] = kb; else kpa[a] = ka;
+}
+// lcx_diag_coal_rate: one accumulator row as the object's real type, normalised as a diag_*_mom result (by dv, then by rhod; a parcel is not divided)
+template <class T>
+__global__ void k_coal_rate_out(size_t n_cell, const unsigned long long *row, int is_m3, const T *dv, const T *rhod, int specific, T *out)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  T v = is_m3 ? T(reinterpret_cast<const double *>(row)[c]) : T(double(row[c]));
+  if (specific) { v = v / dv[c]; v = v / rhod[c]; }
+  out[c] = v;
+}
+// lcx_coal_rates_read: the [LCX_CR_COUNT][n_cell] block as doubles (the number rows converted), out[w * stride + c]
+__global__ void k_coal_rates_f64(size_t n_cell, const unsigned long long *acc, unsigned m3_rows, double *out, size_t stride)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  const unsigned w = blockIdx.y;
+  const unsigned long long *row = acc + size_t(w) * n_cell;
+  out[size_t(w) * stride + c] = (m3_rows >> w) & 1u ? reinterpret_cast<const double *>(row)[c] : double(row[c]);
 }
 
 // ============================================================================================

@@ -317,6 +317,50 @@ def diag_batch_check(reqs, lib=None):
         raise RuntimeError(lib.lcx_last_error().decode())
 
 
+# ---- collision rates per cell (include/lcx_coal_rates.h)
+COAL_RATES = ("acnv_m3", "acnv_nc", "acnv_nr", "accr_m3", "accr_nc", "self_cloud_n", "self_rain_n")     # enum LCX_CR_*, in its order
+
+
+def coal_rate_index(name):
+    """LCX_CR_* of an accumulator's name (one of COAL_RATES, any letter case) or of its number"""
+    if isinstance(name, str):
+        if name.lower() not in COAL_RATES:
+            raise ValueError("libcloudph++: coal_rates: unknown accumulator %r (one of %s)" % (name, ", ".join(COAL_RATES)))
+        return COAL_RATES.index(name.lower())
+    w = int(name)
+    if not 0 <= w < len(COAL_RATES):
+        raise ValueError("libcloudph++: coal_rates: which = %d is outside 0 .. %d" % (w, len(COAL_RATES) - 1))
+    return w
+
+
+def coal_rates_threshold(r_thr):
+    """the threshold radius as lcx_coal_rates_enable takes it: a positive, finite number"""
+    r = float(r_thr)
+    if not (r > 0 and np.isfinite(r)):
+        raise ValueError("libcloudph++: coal_rates: r_thr must be positive and finite")
+    return r
+
+
+def coal_rates_out(out, n_cell):
+    """(address, row stride in doubles, on_device) of an output array of coal_rates: (len(COAL_RATES), n_cell) doubles with unit stride
+    along cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
+    if len(out.shape) != 2 or out.shape[0] != len(COAL_RATES) or out.shape[1] != n_cell:
+        raise ValueError("libcloudph++: coal_rates: out must be 2-D, (%d, n_cell)" % len(COAL_RATES))
+    if isinstance(out, DeviceArray):
+        ptr, strides = out.ptr, out.strides
+    else:
+        if out.dtype != np.float64:
+            raise ValueError("libcloudph++: coal_rates: out must hold float64")
+        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
+            raise ValueError("libcloudph++: coal_rates: unsupported strides")
+        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
+    if n_cell > 1 and strides[1] != 1:
+        raise ValueError("libcloudph++: coal_rates: out must have unit stride along cells")
+    if strides[0] < n_cell:
+        raise ValueError("libcloudph++: coal_rates: out's row stride is below n_cell")
+    return ptr, strides[0], isinstance(out, DeviceArray)
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -812,6 +856,34 @@ class particles_t:
         stride = strides[0] if out.shape[0] > 1 else n_cell                    # (a single row's stride says nothing)
         self._chk(self._f("diag_batch")(self._h, arr, C.c_int(n_req), C.c_void_p(ptr), C.c_size_t(max(stride, 0)), C.c_int(int(on_device))))
         return out
+
+    # -- collision rates per cell (include/lcx_coal_rates.h; no reference counterpart)
+    def coal_rates_enable(self, r_thr):
+        """start (or restart from zero) the per-cell sums of what collisions move between cloud (r_wet < r_thr) and rain; before or
+        after init()"""
+        self._chk(self._f("coal_rates_enable")(self._h, C.c_double(coal_rates_threshold(r_thr))))
+
+    def coal_rates_disable(self):
+        self._chk(self._f("coal_rates_disable")(self._h))
+
+    def coal_rates_info(self):
+        """(enabled, r_thr, coalescence launches tallied since enable or the last reset)"""
+        en, r, n = C.c_int(), C.c_double(), C.c_ulonglong()
+        self._chk(self._f("coal_rates_info")(self._h, C.byref(en), C.byref(r), C.byref(n)))
+        return bool(en.value), r.value, n.value
+
+    def coal_rates(self, reset=False, out=None):
+        """the seven accumulators: a dict name (COAL_RATES) -> ndarray(n_cell) of float64; with out= (a (7, n_cell) float64 numpy array or
+        DeviceArray of the object's device) fills and returns that.  reset: zero them behind the read."""
+        n_cell = self.n_cell
+        arr = np.zeros((len(COAL_RATES), n_cell), dtype=np.float64) if out is None else out
+        ptr, stride, on_device = coal_rates_out(arr, n_cell)
+        self._chk(self._f("coal_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        return {nm: arr[w] for w, nm in enumerate(COAL_RATES)} if out is None else out
+
+    def diag_coal_rate(self, name):
+        """fills outbuf() with one accumulator (a name of COAL_RATES or its number), normalised as a diag_*_mom result"""
+        self._chk(self._f("diag_coal_rate")(self._h, C.c_int(coal_rate_index(name))))
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
