@@ -18,6 +18,7 @@
 #include "../../lcx_state.h"
 #include "../../lcx_diag.h"
 #include "../../lcx_coal_rates.h"
+#include "../../lcx_cond_rates.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -106,6 +107,14 @@ namespace libcloudphxx { namespace lgrngn {
     diag_req_t &dry_mom(int k_) { count = LCX_DIAG_DRY_MOM; k = k_; return *this; }
     diag_req_t &wet_mom(int k_) { count = LCX_DIAG_WET_MOM; k = k_; return *this; }
     diag_req_t &kappa_mom(int k_) { count = LCX_DIAG_KAPPA_MOM; k = k_; return *this; }
+  };
+
+  // the rows of one threshold of particles_t<real_t, HIP>::cond_rates (an extension without a reference counterpart; include/lcx_cond_rates.h
+  // defines each of them); total_dm3 names the row behind the last threshold's
+  enum class cond_rate_t : int
+  {
+    above_dm3 = LCX_CDR_ABOVE_DM3, up_n = LCX_CDR_UP_N, up_m3 = LCX_CDR_UP_M3, down_n = LCX_CDR_DOWN_N, down_m3 = LCX_CDR_DOWN_M3,
+    per_thr = LCX_CDR_PER_THR, total_dm3 = -1
   };
 
   // the accumulators of particles_t<real_t, HIP>::coal_rates (an extension without a reference counterpart; include/lcx_coal_rates.h
@@ -373,6 +382,31 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_coal_rates_read(pimpl->h, out.data(), n_cell, 0, reset ? 1 : 0));
     }
     void diag_coal_rate(coal_rate_t which) { detail::lcx_check(lcx_diag_coal_rate(pimpl->h, int(which))); }
+    // EXTENSION, no reference counterpart (include/lcx_cond_rates.h): per-cell tally of what step_cond's condensation does relative to up to
+    // LCX_CDR_MAX_THR increasing threshold radii -- growth above a threshold, droplets and water crossing it up and down, and the total --
+    // filled by a pass of its own around the condensation while enabled.  cond_rates: out[row * n_cell + cell] with row = 5 t + int(cond_rate_t)
+    // and the total in row 5 K (resized to (5 K + 1) * n_cell), the numbers as doubles; reset zeroes the rows behind the read.  diag_cond_rate
+    // fills outbuf() like a diag_*_mom call.  A snapshot does not hold them: a restored object is disabled.  Not virtual, as above.
+    void cond_rates_enable(const std::vector<real_t> &r_thr)
+    {
+      std::vector<double> r(r_thr.begin(), r_thr.end());
+      detail::lcx_check(lcx_cond_rates_enable(pimpl->h, r.data(), int(r.size())));
+    }
+    void cond_rates_disable() { detail::lcx_check(lcx_cond_rates_disable(pimpl->h)); }
+    void cond_rates(std::vector<double> &out, bool reset = false)
+    {
+      size_t n_cell = 0; int n_thr = 0;
+      detail::lcx_check(lcx_n_cell(pimpl->h, &n_cell));
+      detail::lcx_check(lcx_cond_rates_info(pimpl->h, nullptr, &n_thr, nullptr, nullptr));
+      out.resize(size_t(LCX_CDR_PER_THR * n_thr + 1) * n_cell);
+      detail::lcx_check(lcx_cond_rates_read(pimpl->h, out.data(), n_cell, 0, reset ? 1 : 0));
+    }
+    void diag_cond_rate(cond_rate_t which, int t = 0)
+    {
+      int n_thr = 0;
+      detail::lcx_check(lcx_cond_rates_info(pimpl->h, nullptr, &n_thr, nullptr, nullptr));
+      detail::lcx_check(lcx_diag_cond_rate(pimpl->h, which == cond_rate_t::total_dm3 ? LCX_CDR_PER_THR * n_thr : LCX_CDR_PER_THR * t + int(which)));
+    }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

@@ -28,6 +28,7 @@
 #include "../../include/lcx_state.h"
 #include "../../include/lcx_diag.h"
 #include "../../include/lcx_coal_rates.h"
+#include "../../include/lcx_cond_rates.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -143,6 +144,13 @@ struct IParticles {
   virtual void coal_rates_info(int *, double *, unsigned long long *) { no_coal_rates(); }
   virtual void coal_rates_read(double *, size_t, bool, bool) { no_coal_rates(); }
   virtual void diag_coal_rate(int) { no_coal_rates(); }
+  // condensation rates per cell (include/lcx_cond_rates.h): built for a single-device object
+  [[noreturn]] static void no_cond_rates() { throw std::runtime_error("libcloudph++: cond_rates on a multi-device object is not built"); }
+  virtual void cond_rates_enable(const double *, int) { no_cond_rates(); }
+  virtual void cond_rates_disable() { no_cond_rates(); }
+  virtual void cond_rates_info(int *, int *, double *, unsigned long long *) { no_cond_rates(); }
+  virtual void cond_rates_read(double *, size_t, bool, bool) { no_cond_rates(); }
+  virtual void diag_cond_rate(int) { no_cond_rates(); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -1792,6 +1800,96 @@ struct Particles : IParticles {
                        int((CR_M3_ROWS >> which) & 1u), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
     sync();
   }
+  // ---- condensation rates per cell (include/lcx_cond_rates.h): 5 K + 1 rows per cell, fed by a pass of its own around step_cond's condensation ----
+  // While they are on, step_cond copies rw2 into a scratch column ahead of its first condensation launch (cdr_before) and launches k_cond_rates
+  // behind the last substep (cdr_tally): two launches more, and no condensation kernel is another one.  Storage slots do not move in between
+  // (reorder_storage and the compaction belong to the move and post_copy), so slot i of the column is slot i of A.rw2.  Off, nothing below is
+  // looked at and nothing is allocated.
+  bool cdr_on = false; int cdr_k = 0; double cdr_r_thr[LCX_CDR_MAX_THR] = {0, 0, 0, 0}; unsigned long long cdr_calls = 0;
+  DevBuf<unsigned long long> cdr_acc; DevBuf<T> cdr_rw2_before; DevBuf<double> cdr_out; std::vector<double> cdr_host;
+  int cdr_rows() const { return LCX_CDR_PER_THR * cdr_k + 1; }
+  void cdr_zero() { HIPCHK(hipMemsetAsync(cdr_acc.p, 0, size_t(cdr_rows()) * ncell * sizeof(unsigned long long), st)); cdr_calls = 0; }
+  void cond_rates_enable(const double *r_thr, int n_thr) override
+  {
+    if (n_thr < 1 || n_thr > LCX_CDR_MAX_THR) throw lcx_error("libcloudph++: cond_rates: n_thr = " + std::to_string(n_thr) + " is outside 1 .. " + std::to_string(int(LCX_CDR_MAX_THR)));
+    if (!r_thr) throw lcx_error("libcloudph++: cond_rates: r_thr == NULL");
+    T lo_prev = T(0);
+    for (int t = 0; t < n_thr; ++t) {
+      if (!(r_thr[t] > 0) || !std::isfinite(r_thr[t])) throw lcx_error("libcloudph++: cond_rates: every threshold must be positive and finite");
+      if (t && !(r_thr[t] > r_thr[t - 1])) throw lcx_error("libcloudph++: cond_rates: the thresholds must be strictly increasing");
+      double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, r_thr[t], r_thr[t], lo, hi);
+      if (t && !(T(lo) > lo_prev)) throw lcx_error("libcloudph++: cond_rates: the bounds r_thr^2 of thresholds " + std::to_string(t - 1) + " and " + std::to_string(t) +
+                                                  " are not strictly increasing in the object's real type");
+      lo_prev = T(lo);
+    }
+    if (cdr_acc.p) HIPCHK(hipStreamSynchronize(st));             // (a kernel still queued may read the rows that a larger K re-allocates)
+    cdr_k = n_thr; for (int t = 0; t < LCX_CDR_MAX_THR; ++t) cdr_r_thr[t] = t < n_thr ? r_thr[t] : 0.;
+    cdr_acc.alloc(size_t(cdr_rows()) * ncell);
+    cdr_on = true;
+    cdr_zero();
+  }
+  void cond_rates_disable() override
+  {
+    cdr_on = false; cdr_k = 0; cdr_calls = 0; for (double &r : cdr_r_thr) r = 0;
+    if (cdr_acc.p || cdr_rw2_before.p) { HIPCHK(hipStreamSynchronize(st)); cdr_acc.release(); cdr_rw2_before.release(); cdr_out.release(); }
+  }
+  void cond_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override
+  {
+    if (enabled) *enabled = cdr_on ? 1 : 0;
+    if (n_thr) *n_thr = cdr_k;
+    if (r_thr) for (int t = 0; t < cdr_k; ++t) r_thr[t] = cdr_r_thr[t];
+    if (calls) *calls = cdr_calls;
+  }
+  void cdr_need(const char *what) const { if (!cdr_on) throw lcx_error(std::string("libcloudph++: cond_rates: ") + what + " while the tally is not enabled (lcx_cond_rates_enable)"); }
+  void cond_rates_read(double *out, size_t stride, bool on_device, bool reset) override
+  {
+    cdr_need("read");
+    if (!out) throw lcx_error("libcloudph++: cond_rates: out == NULL");
+    if (stride < ncell) throw lcx_error("libcloudph++: cond_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
+    const int rows = cdr_rows();
+    const dim3 gr(nblk(ncell), rows);
+    if (on_device) hipLaunchKernelGGL(k_cond_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cdr_acc.p, cdr_k, out, stride);
+    else {
+      cdr_out.alloc(size_t(rows) * ncell); cdr_host.resize(size_t(rows) * ncell);
+      hipLaunchKernelGGL(k_cond_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cdr_acc.p, cdr_k, cdr_out.p, ncell);
+      HIPCHK(hipMemcpyAsync(cdr_host.data(), cdr_out.p, cdr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (reset) cdr_zero();
+    sync();
+    if (!on_device) for (int w = 0; w < rows; ++w) memcpy(out + size_t(w) * stride, cdr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
+  }
+  void diag_cond_rate(int row) override
+  {
+    cdr_need("diag_cond_rate");
+    if (!init_called) throw lcx_error("libcloudph++: cond_rates: diag_cond_rate before init()");
+    if (row < 0 || row >= cdr_rows()) throw lcx_error("libcloudph++: cond_rates: row = " + std::to_string(row) + " is outside 0 .. " + std::to_string(cdr_rows() - 1));
+    const int which = row % LCX_CDR_PER_THR;
+    const bool is_n = row < LCX_CDR_PER_THR * cdr_k && (which == LCX_CDR_UP_N || which == LCX_CDR_DOWN_N);
+    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(cdr_acc.p + size_t(row) * ncell),
+                       int(!is_n), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
+    sync();
+  }
+  // step_cond, ahead of the first condensation launch: rw2 as stored, into the scratch column (allocated here: the capacity is not known before init)
+  void cdr_before()
+  {
+    if (!nphys) return;
+    if (cdr_rw2_before.n < A.rw2.n) { HIPCHK(hipStreamSynchronize(st)); cdr_rw2_before.alloc(A.rw2.n); }     // (first use, or the storage has grown)
+    HIPCHK(hipMemcpyAsync(cdr_rw2_before.p, A.rw2.p, nphys * sizeof(T), hipMemcpyDeviceToDevice, st));
+  }
+  // step_cond, behind the last substep
+  template <int K> void cdr_launch()
+  {
+    cond_rates_arg<T, K> a{A.n.p, cdr_rw2_before.p, A.rw2.p, ijk.p, cdr_acc.p, ncell, {}};
+    for (int t = 0; t < K; ++t) { double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, cdr_r_thr[t], cdr_r_thr[t], lo, hi); a.lo[t] = T(lo); }
+    hipLaunchKernelGGL((k_cond_rates<T, K>), dim3(nblk(nphys)), dim3(BS), 0, st, nphys, a);
+  }
+  void cdr_tally()
+  {
+    ++cdr_calls;
+    if (!nphys) return;
+    Range r(this, "cond_rates");
+    switch (cdr_k) { case 1: cdr_launch<1>(); break; case 2: cdr_launch<2>(); break; case 3: cdr_launch<3>(); break; default: cdr_launch<4>(); }
+  }
   void refresh_n_max()
   {
     if (!n_max_stale) return;
@@ -2683,6 +2781,7 @@ struct Particles : IParticles {
     if (ix_ict >= 0 && nphys)                                                            // update_incloud_time, particles_step.ipp:180-181
       hipLaunchKernelGGL(k_incloud_time<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, ijk.p, A.rd3.p, A.kpa.p, A.rw2.p, Tk.p, T(dt), A.ext[ix_ict].p);
     if (opts.cond) {
+      if (cdr_on) cdr_before();                    // (include/lcx_cond_rates.h: rw2 as stored ahead of the first condensation launch)
       // (a measurement switch that names one of the per-substep kernels gets that kernel)
       constexpr unsigned per_substep_variants = LCX_DBG_COND_NO_FUSED_SUBSTEPS | LCX_DBG_COND_FOLD | LCX_DBG_COND_WQ | LCX_DBG_COND_BUDGET | LCX_DBG_COND_PROBE |
                                                 LCX_DBG_COND_LEAN_R3 | LCX_DBG_FINISH_STAGED | LCX_DBG_COND_NO_FOLD;
@@ -2697,6 +2796,7 @@ struct Particles : IParticles {
         cond_substep(opts.RH_max, step, opts.turb_cond);                                 // (hskpng_mfp at substep 0 and hskpng_Tpr inside)
       }
       sstp_save();
+      if (cdr_on) cdr_tally();                     // (behind the last substep, whichever kernels ran it)
       if (!chem_now) { Range r(this, "sync_out"); sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); flush_sync_jobs(); }
     }
     if (chem_now) {                                // (after condensation, ahead of the results going out: particles_step.ipp:269-327)
@@ -3810,6 +3910,7 @@ struct Particles : IParticles {
       skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false;
       sync();
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
+      cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)
     } catch (...) { roll_back(); throw; }
   }
   // what the constructor left zero and a load that failed half-way may have written
@@ -4089,6 +4190,13 @@ int lcx_coal_rates_info(lcx_particles *h, int *enabled, double *r_thr, unsigned 
 int lcx_coal_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
 { LCX_TRY(H->coal_rates_read(out, stride, out_on_device != 0, reset != 0)) }
 int lcx_diag_coal_rate(lcx_particles *h, int which) { LCX_TRY(H->diag_coal_rate(which)) }
+// ---- condensation rates per cell (include/lcx_cond_rates.h) ----
+int lcx_cond_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->cond_rates_enable(r_thr, n_thr)) }
+int lcx_cond_rates_disable(lcx_particles *h) { LCX_TRY(H->cond_rates_disable()) }
+int lcx_cond_rates_info(lcx_particles *h, int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) { LCX_TRY(H->cond_rates_info(enabled, n_thr, r_thr, calls)) }
+int lcx_cond_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
+{ LCX_TRY(H->cond_rates_read(out, stride, out_on_device != 0, reset != 0)) }
+int lcx_diag_cond_rate(lcx_particles *h, int row) { LCX_TRY(H->diag_cond_rate(row)) }
 
 // ---- checkpoint and restart (include/lcx_state.h) ----
 int lcx_snapshot_size(lcx_particles *h, size_t *bytes) { LCX_TRY(*bytes = H->snapshot_size()) }

@@ -2930,6 +2930,77 @@ __global__ void k_coal_rates_f64(size_t n_cell, const unsigned long long *acc, u
   out[size_t(w) * stride + c] = (m3_rows >> w) & 1u ? reinterpret_cast<const double *>(row)[c] : double(row[c]);
 }
 
+// Condensation rates (include/lcx_cond_rates.h): what one step_cond did to every droplet relative to K thresholds, from rw2 as it
+// was ahead of the condensation (rw2_0, the scratch column) and as it is now.  acc is [5 K + 1][n_cell] words of 8 bytes: the M3 rows hold doubles,
+// UP_N and DOWN_N unsigned 64-bit integers.  A slot per lane in storage order, nothing gathered.  Storage is cell-major most of the time, so a wave
+// holds a few runs of equal ijk in adjacent lanes: every row is summed along its runs inside the wave (a segmented suffix sum over __shfl_down, in a
+// fixed order), and the run's first lane issues ONE atomic per row -- none where the run adds nothing to the row, and a row that no lane of the wave
+// feeds is not even summed (a wave of a cloudy cell: TOTAL_DM3 and ABOVE_DM3 of the thresholds below the cloud, K + 1 atomics).  Any storage order is
+// correct: interleaved cells only mean runs of one lane.  The integer sums do not depend on the order, the M3 sums do in their last bits.
+// The design rests on the rate of f64 atomics (MI355X_MICROARCH.md has the f32 rate only): measured (EXPERIMENTS.md 7.12), single-lane adds run at about 2e10 a
+// second, so a storage that advection has drifted from the cell order (runs of one or two lanes) makes this kernel cost most of a step.
+template <class T, int K> struct cond_rates_arg { const n_t *n; const T *rw2_0, *rw2_1; const uint32_t *ijk; unsigned long long *acc; size_t n_cell; T lo[K]; };
+template <class V>
+__device__ __forceinline__ V cdr_run_sum(V v, const unsigned run)         // the sum of v over the lanes of this lane's run from this lane on
+{
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const V o = __shfl_down(v, d); const unsigned r = __shfl_down(run, d);
+    if (lane_id() + unsigned(d) < unsigned(WAVE) && r == run) v += o;
+  }
+  return v;
+}
+template <class T, int K>
+__global__ void __launch_bounds__(BS) k_cond_rates(size_t n_part, const cond_rates_arg<T, K> a)
+{
+  const size_t i = gid();
+  uint32_t c = DEAD_CELL; unsigned long long mu = 0ull; double m = 0., c0 = 0., c1 = 0.; T x0 = T(0), x1 = T(0);
+  if (i < n_part) {
+    const n_t mult = a.n[i]; const uint32_t ci = a.ijk[i];
+    if (mult != 0 && size_t(ci) < a.n_cell) {
+      c = ci; mu = (unsigned long long)mult; m = double(mult); x0 = a.rw2_0[i]; x1 = a.rw2_1[i];
+      const double d0 = double(x0), d1 = double(x1);
+      c0 = d0 * sqrt(d0); c1 = d1 * sqrt(d1);
+    }
+  }
+  const bool live = c != DEAD_CELL;
+  if (!__ballot(live)) return;
+  // runs: a lane begins one where its cell differs from its left neighbour's (a slot that takes no part is a run of its own, adding nothing)
+  const uint32_t left = __shfl_up(c, 1);
+  const bool head = lane_id() == 0 || left != c || !live;
+  const unsigned long long heads = __ballot(head);
+  const unsigned run = unsigned(__popcll(heads & (~0ull >> (WAVE - 1 - lane_id()))));
+  unsigned long long *row = a.acc + (live ? c : 0u);
+  auto add_m3 = [&](int w, double v) {
+    const double s = cdr_run_sum(v, run);
+    if (head && live && s != 0.) unsafeAtomicAdd(reinterpret_cast<double *>(row + size_t(w) * a.n_cell), s);
+  };
+  auto add_n = [&](int w, unsigned long long v) {
+    const unsigned long long s = cdr_run_sum(v, run);
+    if (head && live && s) atomicAdd(row + size_t(w) * a.n_cell, s);
+  };
+  const double dm3 = m * (c1 - c0);
+  if (__ballot(dm3 != 0.)) add_m3(LCX_CDR_PER_THR * K, dm3);
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    const bool ab0 = live && !(x0 < a.lo[t]), ab1 = live && !(x1 < a.lo[t]);
+    const bool stay = ab0 && ab1, up = live && !ab0 && ab1, down = ab0 && !ab1;
+    if (__ballot(stay && dm3 != 0.)) add_m3(LCX_CDR_PER_THR * t + LCX_CDR_ABOVE_DM3, stay ? dm3 : 0.);
+    if (__ballot(up)) { add_n(LCX_CDR_PER_THR * t + LCX_CDR_UP_N, up ? mu : 0ull); add_m3(LCX_CDR_PER_THR * t + LCX_CDR_UP_M3, up ? m * c1 : 0.); }
+    if (__ballot(down)) { add_n(LCX_CDR_PER_THR * t + LCX_CDR_DOWN_N, down ? mu : 0ull); add_m3(LCX_CDR_PER_THR * t + LCX_CDR_DOWN_M3, down ? m * c0 : 0.); }
+  }
+}
+// lcx_cond_rates_read: the [5 K + 1][n_cell] block as doubles (the two number rows of every threshold converted), out[row * stride + c]
+__global__ void k_cond_rates_f64(size_t n_cell, const unsigned long long *acc, int n_thr, double *out, size_t stride)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  const unsigned w = blockIdx.y;
+  const unsigned which = w % unsigned(LCX_CDR_PER_THR);
+  const bool is_n = int(w) < LCX_CDR_PER_THR * n_thr && (which == LCX_CDR_UP_N || which == LCX_CDR_DOWN_N);
+  const unsigned long long *row = acc + size_t(w) * n_cell;
+  out[size_t(w) * stride + c] = is_n ? double(row[c]) : reinterpret_cast<const double *>(row)[c];
+}
+
 // ============================================================================================
 // advection + sedimentation + subsidence + boundary conditions in ONE pass
 // (adve.ipp:28-165,169-183; sedi.ipp:13-25; subs.ipp:13-25; bcnd.ipp:99-368)

@@ -361,6 +361,63 @@ def coal_rates_out(out, n_cell):
     return ptr, strides[0], isinstance(out, DeviceArray)
 
 
+# ---- condensation rates per cell (include/lcx_cond_rates.h)
+COND_RATES = ("above_dm3", "up_n", "up_m3", "down_n", "down_m3")     # enum LCX_CDR_*, in its order: the rows of one threshold
+COND_RATES_MAX_THR = 4                                               # LCX_CDR_MAX_THR
+COND_RATES_TOTAL = "total_dm3"                                       # the last row, 5 K
+
+
+def cond_rates_thresholds(r_thr):
+    """the thresholds as lcx_cond_rates_enable takes them, from a scalar or a sequence: 1 .. 4 positive, finite, strictly increasing radii"""
+    r = [float(x) for x in np.atleast_1d(np.asarray(r_thr, dtype=np.float64)).ravel()]
+    if not 1 <= len(r) <= COND_RATES_MAX_THR:
+        raise ValueError("libcloudph++: cond_rates: n_thr = %d is outside 1 .. %d" % (len(r), COND_RATES_MAX_THR))
+    if not all(x > 0 and np.isfinite(x) for x in r):
+        raise ValueError("libcloudph++: cond_rates: every threshold must be positive and finite")
+    if any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError("libcloudph++: cond_rates: the thresholds must be strictly increasing")
+    return r
+
+
+def cond_rate_index(name, t=0, n_thr=COND_RATES_MAX_THR):
+    """the row of a name of COND_RATES at threshold t (or of "total_dm3"), or of a row number, among 5 n_thr + 1 rows"""
+    n_rows = len(COND_RATES) * n_thr + 1
+    if isinstance(name, str):
+        if name.lower() == COND_RATES_TOTAL:
+            return n_rows - 1
+        if name.lower() not in COND_RATES:
+            raise ValueError("libcloudph++: cond_rates: unknown row %r (one of %s, %s)" % (name, ", ".join(COND_RATES), COND_RATES_TOTAL))
+        t = int(t)
+        if not 0 <= t < n_thr:
+            raise ValueError("libcloudph++: cond_rates: t = %d is outside 0 .. %d" % (t, n_thr - 1))
+        return len(COND_RATES) * t + COND_RATES.index(name.lower())
+    w = int(name)
+    if not 0 <= w < n_rows:
+        raise ValueError("libcloudph++: cond_rates: row = %d is outside 0 .. %d" % (w, n_rows - 1))
+    return w
+
+
+def cond_rates_out(out, n_thr, n_cell):
+    """(address, row stride in doubles, on_device) of an output array of cond_rates: (5 n_thr + 1, n_cell) doubles with unit stride
+    along cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
+    n_rows = len(COND_RATES) * n_thr + 1
+    if len(out.shape) != 2 or out.shape[0] != n_rows or out.shape[1] != n_cell:
+        raise ValueError("libcloudph++: cond_rates: out must be 2-D, (%d, n_cell)" % n_rows)
+    if isinstance(out, DeviceArray):
+        ptr, strides = out.ptr, out.strides
+    else:
+        if out.dtype != np.float64:
+            raise ValueError("libcloudph++: cond_rates: out must hold float64")
+        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
+            raise ValueError("libcloudph++: cond_rates: unsupported strides")
+        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
+    if n_cell > 1 and strides[1] != 1:
+        raise ValueError("libcloudph++: cond_rates: out must have unit stride along cells")
+    if strides[0] < n_cell:
+        raise ValueError("libcloudph++: cond_rates: out's row stride is below n_cell")
+    return ptr, strides[0], isinstance(out, DeviceArray)
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -884,6 +941,41 @@ class particles_t:
     def diag_coal_rate(self, name):
         """fills outbuf() with one accumulator (a name of COAL_RATES or its number), normalised as a diag_*_mom result"""
         self._chk(self._f("diag_coal_rate")(self._h, C.c_int(coal_rate_index(name))))
+
+    # -- condensation rates per cell (include/lcx_cond_rates.h; no reference counterpart)
+    def cond_rates_enable(self, r_thr):
+        """start (or restart from zero) the per-cell tally of what step_cond's condensation does relative to the threshold radii r_thr (a
+        scalar or up to four increasing values); before or after init()"""
+        r = cond_rates_thresholds(r_thr)
+        self._chk(self._f("cond_rates_enable")(self._h, (C.c_double * len(r))(*r), C.c_int(len(r))))
+
+    def cond_rates_disable(self):
+        self._chk(self._f("cond_rates_disable")(self._h))
+
+    def cond_rates_info(self):
+        """(enabled, the thresholds as a tuple, step_cond calls tallied since enable or the last reset)"""
+        en, k, r, n = C.c_int(), C.c_int(), (C.c_double * COND_RATES_MAX_THR)(), C.c_ulonglong()
+        self._chk(self._f("cond_rates_info")(self._h, C.byref(en), C.byref(k), r, C.byref(n)))
+        return bool(en.value), tuple(r[t] for t in range(k.value)), n.value
+
+    def cond_rates(self, reset=False, out=None):
+        """the rows: a dict with "total_dm3" (n_cell,) and "above_dm3", "up_n", "up_m3", "down_n", "down_m3" (K, n_cell), float64; with out= (a
+        (5 K + 1, n_cell) float64 numpy array or DeviceArray of the object's device) fills and returns that.  reset: zero them behind the read."""
+        n_cell, n_thr = self.n_cell, max(len(self.cond_rates_info()[1]), 1)
+        n_per = len(COND_RATES)
+        arr = np.zeros((n_per * n_thr + 1, n_cell), dtype=np.float64) if out is None else out
+        ptr, stride, on_device = cond_rates_out(arr, n_thr, n_cell)
+        self._chk(self._f("cond_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        if out is not None:
+            return out
+        res = {nm: arr[w:n_per * n_thr:n_per] for w, nm in enumerate(COND_RATES)}
+        res[COND_RATES_TOTAL] = arr[n_per * n_thr]
+        return res
+
+    def diag_cond_rate(self, name_or_row, t=0):
+        """fills outbuf() with one row (a name of COND_RATES at threshold t, "total_dm3", or a row number), normalised as a diag_*_mom result"""
+        n_thr = max(len(self.cond_rates_info()[1]), 1)
+        self._chk(self._f("diag_cond_rate")(self._h, C.c_int(cond_rate_index(name_or_row, t, n_thr))))
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
