@@ -238,8 +238,13 @@ enum lcx_dbg2 {
                                         * and its workgroups ("raw_coal_wg" = { workgroups that left before ranking, workgroups launched }, of those launches) */
   LCX_DBG2_NO_COAL_RANK_EXIT = 1 << 1, /* k_coal_ranked with a bound ranks in every workgroup, as in round 8, instead of leaving ahead of the ranking where
                                         * the workgroup keeps no pair (the same bits) */
-  LCX_DBG2_COAL_RANK_EXIT_ALWAYS = 1 << 2 /* tests: the form with the exit in every bound launch, also where the last launch's counters showed fewer than
+  LCX_DBG2_COAL_RANK_EXIT_ALWAYS = 1 << 2, /* tests: the form with the exit in every bound launch, also where the last launch's counters showed fewer than
                                         * 0.24 of the workgroups leaving ("raw_coal_exit": launches of the last lcx_step_async in that form) */
+  LCX_DBG2_NO_COAL_PREVOTE = 1 << 3    /* the form with the exit without the per-cell vote ahead of the launch (k_coal_umin, k_coal_cellvote): every workgroup
+                                        * loads its cells' numbers, draws and votes for itself, as in round 9 (the same bits).  "raw_coal_prevote" = { launches
+                                        * of the last lcx_step_async that were handed the tiles' flags, tiles flagged off, tiles, launches that fell back because
+                                        * the draws were made for another call, seed or set of cells } and, with LCX_DBG2_COAL_SKIP_COUNT (no workgroup then
+                                        * leaves on its flag), the workgroups flagged off whose own vote kept a pair: always 0 */
 };
 
 /* lcx_get_state_u64("raw_mode") = { strict_fp, cond_solver, the kernel of the last condensation launch (below; 0: none yet), dbg_flags } as

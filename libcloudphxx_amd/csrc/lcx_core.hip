@@ -342,6 +342,12 @@ struct Particles : IParticles {
   // scan that rewrites cell_start, a host synchronisation -- makes `st` wait for the ranking first (join_rank): ordered by construction.
   hipStream_t st_rank = nullptr; hipEvent_t ev_fork = nullptr, ev_rank = nullptr; mutable bool rank_pending = false;
   void join_rank() const { if (rank_pending) { rank_pending = false; HIPCHK(hipStreamWaitEvent(st, ev_rank, 0)); } }
+  void make_side_stream()
+  {
+    if (st_rank) return;
+    HIPCHK(hipStreamCreateWithFlags(&st_rank, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_rank, hipEventDisableTiming));
+  }
   // The shuffled in-cell order of a carried re-sort may be OWED instead of made (rank_owed): the scatter has left every cell's ids in arrival
   // order, the flags (sorted, sorted_shuffled, shuffle_fresh) say what the order will be once ranked with the salts deferred_rs, and nothing
   // has been launched.  The production coalescence kernel ranks for itself in LDS (k_coal_ranked, coal()) and needs no order in memory; whoever
@@ -417,6 +423,16 @@ struct Particles : IParticles {
     for (int i = n_pairs; i < skip_sample_n; i += 2) { left += h[i]; launched += h[i + 1]; }
     if (launched && left * 100 < launched * COAL_EXIT_MIN_PERCENT) exit_pause = COAL_EXIT_PAUSE;          // (a launch in round 8's form counts no workgroups)
   }
+  // ---- the cells' vote ahead of the EXIT launch (round 10; lcx_coal_prevote.hpp, k_coal_umin, k_coal_cellvote) ----
+  // step_async launches k_coal_umin on the side stream beside the velocity pass, for the call number that coal() will hand to rand_u01; coal() makes
+  // `st` wait for it, lets the cells vote and hands the tiles' flags to the kernel -- if the draws were made for exactly the call, seed and cells that
+  // the launch is about to use (pv_*_of), else the launch is round 9's and pv_fallback counts it.  Results cannot depend on it: the same bits.
+  DevBuf<T> coal_umin; DevBuf<uint32_t> coal_tile_flag; DevBuf<unsigned long long> coal_pv_disagree;
+  hipEvent_t ev_umin_fork = nullptr, ev_umin = nullptr;
+  bool umin_pending = false, umin_made = false;          // (launched and not yet joined by `st`; launched in this step_async)
+  uint64_t pv_call_of = 0, pv_seed_of = 0, pv_cells_of = 0; size_t pv_npart_of = 0;
+  int pv_used = 0, pv_fallback = 0; size_t pv_tiles = 0; // ("raw_coal_prevote", of the last step_async)
+  void join_umin() { if (umin_pending) { umin_pending = false; HIPCHK(hipStreamWaitEvent(st, ev_umin, 0)); } }
   bool coal_bound_armed = false;             // step_async's own hskpng_vterm has just left the maxima: the FIRST coalescence substep may use them
   int last_coal_skip = 0;                    // ("raw_coal_skip": the coalescence launches of the last step_async that used a bound)
   unsigned long long coal_bound_unused = 0;  // ("raw_coal_bound_unused": step_asyncs of this object whose velocity pass collected maxima that no launch used --
@@ -540,6 +556,7 @@ struct Particles : IParticles {
   ~Particles() override
   {
     if (st_rank) { (void)hipStreamSynchronize(st_rank); (void)hipStreamDestroy(st_rank); (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_rank); }
+    if (ev_umin) { (void)hipEventDestroy(ev_umin_fork); (void)hipEventDestroy(ev_umin); }
     if (st) (void)hipStreamSynchronize(st);
     for (auto &e : prof_events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
     for (hipEvent_t e : prof_pool) (void)hipEventDestroy(e);
@@ -1558,10 +1575,7 @@ struct Particles : IParticles {
         sorted = true; sorted_shuffled = true; shuffle_fresh = true; last_shuffle_rs = deferred_rs;
       }
       else if (!dbg(LCX_DBG_NO_RANK_OVERLAP) && profiling != 1 && meta_version == cells_version) {
-        if (!st_rank) {
-          HIPCHK(hipStreamCreateWithFlags(&st_rank, hipStreamNonBlocking));
-          HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_rank, hipEventDisableTiming));
-        }
+        make_side_stream();
         HIPCHK(hipEventRecord(ev_fork, st));
         HIPCHK(hipStreamWaitEvent(st_rank, ev_fork, 0));
         {
@@ -1898,6 +1912,25 @@ struct Particles : IParticles {
     if (nphys) hipLaunchKernelGGL(k_n_max, dim3(std::min(nblk(nphys), 2048u)), dim3(BS), 0, st, nphys, (const n_t *)A.n.p, coal_n_max.p);
     n_max_stale = false;
   }
+  // step_async, ahead of the velocity pass: the smallest draw of every cell's pairs, on the side stream (beside that pass: it waits for memory, this
+  // kernel only multiplies integers).  Launched where the step's first coalescence launch will be the EXIT form as far as can be known here; the call
+  // number is the one coal() will hand to rand_u01 -- the next one, or the one after where coal() draws the shuffle's salts first.  rng_call is not
+  // advanced.  What the draws were made for is kept with them, and coal() compares (a mismatch: round 9's launch, pv_fallback).
+  void launch_umin(bool want_bound)
+  {
+    umin_made = false; pv_used = 0; pv_fallback = 0; pv_tiles = 0;
+    const bool exit_form = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
+    if (!want_bound || !exit_form || dbg2(LCX_DBG2_NO_COAL_PREVOTE) || npart < 2 || !ncell) return;
+    make_side_stream();
+    if (!ev_umin) { HIPCHK(hipEventCreateWithFlags(&ev_umin_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_umin, hipEventDisableTiming)); }
+    coal_umin.alloc(ncell);
+    pv_call_of = rng_call + 1 + (coal_owes_unshuffled_cells() ? 1 : 0); pv_seed_of = uint64_t(uint32_t(seed_now())); pv_cells_of = cells_version; pv_npart_of = npart;
+    HIPCHK(hipEventRecord(ev_umin_fork, st));                  // (cell_start is final since the last scan, on `st`)
+    HIPCHK(hipStreamWaitEvent(st_rank, ev_umin_fork, 0));
+    hipLaunchKernelGGL(k_coal_umin<T>, dim3(nblk(ncell * 8)), dim3(BS), 0, st_rank, ncell, (const uint32_t *)cell_start.p, pv_call_of, pv_seed_of, coal_umin.p);
+    HIPCHK(hipEventRecord(ev_umin, st_rank));
+    umin_pending = umin_made = true;
+  }
   void coal(double dt_sub, bool turb_coal = false, bool first_substep = true)
   {
     const bool bound_armed = coal_bound_armed && first_substep;      // (the maxima of step_async's own velocity pass: this call or none)
@@ -1922,7 +1955,7 @@ struct Particles : IParticles {
     // reads the order (pay_rank) or the step's re-sort makes it void.
     if (first_substep && coal_ranks_owed_order() && !rs.arr) {
       coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
-      const dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));
+      dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));              // (a workgroup per tile; with the tiles' flags: per COAL_TILES_PER_WG tiles)
       last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
       coal_skip_args<T> ska{};
       bool exits = false;
@@ -1932,8 +1965,24 @@ struct Particles : IParticles {
         exits = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
         if (!exits && exit_pause > 0) --exit_pause;
         if (exits) ++last_coal_exit;
+        // the cells' vote (round 10): the draws that step_async had made beside the velocity pass, if they are this launch's; the flags of the tiles
+        const uint32_t *flags = nullptr;
+        if (exits && umin_made) {
+          umin_made = false;
+          join_umin();
+          if (pv_call_of == rs.call && pv_seed_of == rs.seed && pv_cells_of == cells_version && pv_npart_of == npart) {
+            coal_tile_flag.alloc(gr.x);
+            HIPCHK(hipMemsetAsync(coal_tile_flag.p, 0, size_t(gr.x) * sizeof(uint32_t), st));
+            hipLaunchKernelGGL(k_coal_cellvote<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const uint32_t *)cell_start.p, (const uint32_t *)coal_cmax.p, (const T *)dv.p,
+                               (const T *)coal_umin.p, (const n_t *)coal_n_max.p, (const T *)coal_emax.p, n_emax, T(kernel_r_max), T(dt_sub), coal_tile_flag.p, uint64_t(gr.x));
+            flags = coal_tile_flag.p; pv_tiles = gr.x; ++pv_used;
+          }
+          else ++pv_fallback;     // (defensive: no path reaches it today -- step_async asks for a bound only where coal() neither re-sorts nor draws
+                                  // anything but the salts counted above, and no test takes it; it keeps a later change to either from using stale draws)
+        }
         ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p,
-                                counted && exits ? coal_skip_cnt.p + 2 : nullptr};
+                                counted && exits ? coal_skip_cnt.p + 2 : nullptr, flags, counted && flags ? coal_pv_disagree.p : nullptr};
+        if (flags) gr.x = (gr.x + COAL_TILES_PER_WG - 1) / COAL_TILES_PER_WG;
         if (counted && !exits) coal_wg_no_exit += gr.x;
         ++last_coal_skip;
       }
@@ -1947,7 +1996,8 @@ struct Particles : IParticles {
           hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
                              deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
         };
-        if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL>); else launch(k_coal_ranked<T, false, true, true, TL>); }
+        if (ska.cmax && exits && ska.flags) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL, true>); else launch(k_coal_ranked<T, false, true, true, TL, true>); }
+        else if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL>); else launch(k_coal_ranked<T, false, true, true, TL>); }
         else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, false, TL>); else launch(k_coal_ranked<T, false, true, false, TL>); }
         else if (coal_marks_dead) launch(k_coal_ranked<T, true, false, false, TL>); else launch(k_coal_ranked<T, false, false, false, TL>);
       };
@@ -2843,7 +2893,7 @@ struct Particles : IParticles {
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
     last_coal_ranked = 0; last_coal_skip = 0; last_coal_exit = 0; coal_bound_armed = false;
-    if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) coal_skip_cnt.alloc_zero(4, st);
+    if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) { coal_skip_cnt.alloc_zero(4, st); coal_pv_disagree.alloc_zero(1, st); }
     coal_wg_no_exit = 0;
     vt_fix_pending = false;                           // (a flag of one step_async: nothing of an earlier call is pending)
     last_async_coal = opts.coal != 0;
@@ -2857,6 +2907,7 @@ struct Particles : IParticles {
     if (paused) --skip_pause;
     const bool want_bound = opts.coal && !paused && coal_skip_wanted();
     if (want_bound) refresh_n_max();
+    launch_umin(want_bound);
     if (opts.sedi || opts.coal || opts.cond) coal_bound_armed = hskpng_vterm(false, want_bound);
     const bool bound_collected = coal_bound_armed;
     if (opts.coal) {
@@ -2874,6 +2925,7 @@ struct Particles : IParticles {
       release_replay_keep();
       hskpng_approximate_rc2_invalid();                                                  // particles_step.ipp:402-403
     }
+    join_umin(); umin_made = false;                   // (draws that no launch took: `st` still waits for them ahead of whatever rewrites cell_start)
     // single device, > 0 dimensions: advection + sedimentation + boundary + re-indexing in ONE pass over the positions
     if ((opts.turb_adve || opts.turb_cond) && nphys) sgs_turbulence(opts);              // particles_step.ipp:406-427
     turb_adve_now = opts.turb_adve;
@@ -3121,6 +3173,12 @@ struct Particles : IParticles {
       if (dbg2(LCX_DBG2_COAL_SKIP_COUNT) && coal_skip_cnt.p) { auto h = d2h(coal_skip_cnt.p, 4); v[0] = h[2]; v[1] = h[3] + coal_wg_no_exit; }
     }
     else if (s == "raw_coal_exit") v.assign(1, (unsigned long long)last_coal_exit);
+    else if (s == "raw_coal_prevote") {            // of the last step_async: launches handed the tiles' flags, tiles flagged off, tiles, launches that fell back; LCX_DBG2_COAL_SKIP_COUNT: + disagreements
+      unsigned long long off = 0;
+      if (pv_used && pv_tiles) { auto h = d2h(coal_tile_flag.p, pv_tiles); for (auto x : h) off += x == 0u; }
+      v = {(unsigned long long)pv_used, off, (unsigned long long)pv_tiles, (unsigned long long)pv_fallback};
+      if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) v.push_back(coal_pv_disagree.p ? d2h(coal_pv_disagree.p, 1)[0] : 0ull);
+    }
     else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
@@ -3907,7 +3965,7 @@ struct Particles : IParticles {
       }
       deferred_rs.un = nullptr; last_shuffle_rs.un = nullptr;
       should_now_run_async = should_now_run_cond = selected_before_counting = false;
-      skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false;
+      skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false; umin_made = false; pv_used = 0; pv_fallback = 0; pv_tiles = 0;
       sync();
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)

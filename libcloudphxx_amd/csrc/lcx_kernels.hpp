@@ -13,6 +13,7 @@
 #include "lcx_math.hpp"
 #include "lcx_cond_wq.hpp"
 #include "lcx_diag_plan.hpp"
+#include "lcx_coal_prevote.hpp"
 
 namespace lcx {
 
@@ -2348,7 +2349,7 @@ template <class T> struct coal_kernel_cfg {
   const T *eta, *rhod, *diss;     // per-cell fields of the turbulent (Onishi) kernel; diss == nullptr: dissipation rate 0 (opts.turb_coal off)
 };
 
-__device__ __forceinline__ int kernel_index(n_t R) { return R <= 100. ? int(R) : int(100 + (R - 100.) / 10.); }
+// (kernel_index: lcx_coal_prevote.hpp, shared with the host)
 __device__ __forceinline__ size_t kernel_vector_index(int i, int j, n_t nup)
 {
   return i >= j ? size_t(0.5 * i * (i + 1) + j + nup) : size_t(0.5 * j * (j + 1) + i + nup);
@@ -2550,6 +2551,10 @@ template <class T> struct coal_skip_args {       // what the kernel is handed (c
   unsigned long long *wg;                        // the EXIT form, LCX_DBG2_COAL_SKIP_COUNT: {workgroups that left before ranking, workgroups launched}, one atomic
                                                  // each per workgroup; else sample + 64 takes 32 such pairs from every 64th workgroup (poll_skip_sample: the
                                                  // exit pays only where workgroups do leave)
+  const uint32_t *flags;                         // the EXIT form, round 10: one word per workgroup's tile, 0 where the cells' vote ahead of the launch
+                                                 // (k_coal_cellvote) found no cell with a kept pair in it; nullptr: every workgroup votes for itself
+  unsigned long long *disagree;                  // LCX_DBG2_COAL_SKIP_COUNT with flags: no workgroup leaves on its flag, and one whose flag is 0 and whose
+                                                 // own vote keeps a pair adds one here
 };
 template <class T> struct coal_skip {            // what a lane has fetched of it ahead of the ranking, for the cells of its positions p0 and p0 + 1
   uint32_t r0, v0, r1, v1; T dv0, dv1, n_max, r_max; const T *emax; int n_emax; unsigned long long *cnt;
@@ -2583,24 +2588,15 @@ coal_owned(coal_own &o, const size_t p0, const bool has2, const uint32_t c0, con
 template <class T>
 __device__ __forceinline__ T coal_scale(const coal_own &o)
 {
-  const n_t nn = o.end - o.off;
-  return nn > 1 ? (T(nn * (nn - 1)) / 2) / (nn / 2) : T(0);                    // scale_factor, coal.ipp:99-107
+  return coal_scale_of<T>(n_t(o.end - o.off));                                 // scale_factor, coal.ipp:99-107 (lcx_coal_prevote.hpp)
 }
 // whether the pair's random number rules the collision out; every lane that owns a pair calls it (the counters are per wave)
 template <class T>
 __device__ __forceinline__ bool
 coal_skipped(const coal_own &o, const T scl, const T dt, const u01_src<T> &rs, const coal_skip<T> *sk, T &u_pre, T &dvc_pre)
 {
-  const T rm = T(__uint_as_float(o.second ? sk->r1 : sk->r0)), vm = T(__uint_as_float(o.second ? sk->v1 : sk->v0));
   dvc_pre = o.second ? sk->dv1 : sk->dv0;
-  T bound = T(__uint_as_float(CMAX_POISON));                                   // NaN
-  const T r_um = sqrt(rm) * T(1e6) * T(1 + 1. / 1024);
-  if (r_um < sk->r_max - T(11) && vm < T(3e38)) {                              // (false for a NaN)
-    const n_t x0 = r_um >= T(100) ? n_t(floor(r_um / 10) * 10) : n_t(floor(r_um));
-    const int ie = kernel_index(x0);
-    bound = dt / dvc_pre * scl * sk->n_max * T(cst<T>::pi * 4) * rm * vm * sk->emax[ie < sk->n_emax ? ie : sk->n_emax - 1] * T(1 + 1. / 1024);
-    if (bound < T(1e-30)) bound = T(1e-30);
-  }
+  const T bound = coal_bound<T>(o.second ? sk->r1 : sk->r0, o.second ? sk->v1 : sk->v0, dvc_pre, scl, dt, sk->n_max, sk->r_max, sk->emax, sk->n_emax);   // (lcx_coal_prevote.hpp)
   u_pre = philox::u01<T>(o.p, rs.call, rs.seed);
   const bool skip = bound < T(1) && u_pre >= bound;
   if (sk->cnt) {
@@ -2701,7 +2697,7 @@ coal_pair(const size_t p0, const bool has2, const uint32_t c0, const uint32_t c1
 // what a lane of k_coal_ranked<.., SKIP> fetches of the bound for the cells of its positions p0 and p0 + 1
 template <class T>
 __device__ __forceinline__ void
-coal_skip_fetch(coal_skip<T> &sk, const bool pair_lane, const uint32_t c0, const uint32_t c1, const T *dv, const T r_max, const T *emax_l, const coal_skip_args<T> &ska)
+coal_skip_fetch(coal_skip<T> &sk, const uint32_t tile, const bool pair_lane, const uint32_t c0, const uint32_t c1, const T *dv, const T r_max, const T *emax_l, const coal_skip_args<T> &ska)
 {
   struct alignas(8) pairU { uint32_t a, b; };
   pairU m0{CMAX_POISON, CMAX_POISON}, m1{CMAX_POISON, CMAX_POISON};
@@ -2712,7 +2708,7 @@ coal_skip_fetch(coal_skip<T> &sk, const bool pair_lane, const uint32_t c0, const
   }
   sk.r0 = m0.a; sk.v0 = m0.b; sk.r1 = m1.a; sk.v1 = m1.b;
   sk.n_max = T(*ska.n_max); sk.r_max = r_max; sk.emax = emax_l; sk.n_emax = ska.n_emax;
-  sk.cnt = ska.cnt ? ska.cnt : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
+  sk.cnt = ska.cnt ? ska.cnt : ska.sample && (tile & 63u) == 0u ? ska.sample + 2 * ((tile >> 6) & 31u) : nullptr;
 }
 // TALLY: the collision rates' accumulators are fed (coal_tally_event); without it the argument is empty and the kernel is what it was
 template <class T, bool ONISHI, bool TAB = false, bool TALLY = false>
@@ -2762,11 +2758,13 @@ constexpr int COAL_RANKED_POS = 2 * BS;
 // The counters mean what they meant: every lane that owns a pair counts it, skipped or not, ahead of the exit.
 constexpr int EMAX_CAP = 256;
 // TALLY: as in k_coal, in every form (a pair that the bound skips cannot collide and adds nothing)
-template <class T, bool MARK, bool SKIP = false, bool EXIT = false, bool TALLY = false>
-__global__ void __launch_bounds__(BS)
-k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
-              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {},
-              coal_tally_arg<T, TALLY> ta = {})
+// One tile: the 2 BS positions from tile * 2 BS on.  Every return ahead of the last barrier is uniform.  Returns whether the workgroup has touched
+// its LDS (a workgroup that goes on to another tile passes a barrier first, k_coal_ranked below).
+template <class T, bool MARK, bool SKIP, bool EXIT, bool TALLY>
+__device__ __forceinline__ bool
+coal_ranked_tile(const uint32_t tile, size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, const rng_src &r,
+                 n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, const coal_skip_args<T> &ska,
+                 const coal_tally_arg<T, TALLY> &ta)
 {
   using KEY = uint32_t;
   constexpr int CAP = 4 * BS, OWN = COAL_RANKED_POS;
@@ -2780,14 +2778,23 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
   if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
   static_assert(SKIP || !EXIT, "the exit is the bound's");
-  const size_t P0 = size_t(blockIdx.x) * OWN;
+  const size_t P0 = size_t(tile) * OWN;
   const uint32_t t = threadIdx.x;
   [[maybe_unused]] unsigned long long *wgc = nullptr;
   if constexpr (EXIT) {
-    wgc = ska.wg ? ska.wg : ska.sample && (blockIdx.x & 63u) == 0u ? ska.sample + 64 + 2 * ((blockIdx.x >> 6) & 31u) : nullptr;
+    wgc = ska.wg ? ska.wg : ska.sample && (tile & 63u) == 0u ? ska.sample + 64 + 2 * ((tile >> 6) & 31u) : nullptr;
     if (wgc && t == 0) atomicAdd(wgc + 1, 1ull);
   }
-  if (P0 + 1 >= n_part) return;                        // (uniform)
+  if (P0 + 1 >= n_part) return false;                  // (uniform)
+  [[maybe_unused]] bool flagged_off = false;
+  if constexpr (EXIT) {
+    // round 10: the cells have voted ahead of the launch.  A tile without a kept cell is left on one scalar load, before anything else is read or
+    // written.  Every 64th tile feeds the host's sample (poll_skip_sample) and votes as before, so that the host decides from what it did.
+    if (ska.flags && !(ska.sample && (tile & 63u) == 0u) && ska.flags[tile] == 0u) {                  // (uniform)
+      if (!ska.disagree) return false;
+      flagged_off = true;
+    }
+  }
   const size_t p0 = P0 + 2 * t;
   const bool pair_lane = p0 + 1 < n_part, has2 = p0 + 2 < n_part;
   // what coal_pair needs of the cells, fetched up front as in k_coal
@@ -2800,7 +2807,7 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if constexpr (EXIT) {
     if (int(t) < ska.n_emax) emax_l[t] = ska.emax[t];             // (n_emax <= EMAX_CAP = BS: the host launches this form only then)
     if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
-    coal_skip_fetch<T>(sk, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
+    coal_skip_fetch<T>(sk, tile, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
     __syncthreads();                                              // (emax_l)
     if (pair_lane && coal_owned<T>(own, p0, has2, c0, c1, c2, off0, end0, off1, end1, (T *)nullptr)) {
       scl = coal_scale<T>(own);
@@ -2808,8 +2815,9 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
     }
     if (!__syncthreads_or(kept)) {                                // (uniform: nobody of this workgroup would read the order)
       if (wgc && t == 0) atomicAdd(wgc, 1ull);
-      return;
+      return true;
     }
+    if (flagged_off && t == 0) atomicAdd(ska.disagree, 1ull);     // (LCX_DBG2_COAL_SKIP_COUNT: the cells' vote would have left a workgroup that keeps a pair)
   }
   const size_t last = (P0 + OWN < n_part ? P0 + OWN + 1 : n_part) - 1;       // the last position whose id a lane of this workgroup may need
   // the four entries of the window
@@ -2824,7 +2832,7 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   if (t == WAVE) { const uint32_t c = sorted_ijk[last]; bounds[1] = cell_start[c + 1]; bounds[3] = cell_start[c]; }   // (a wave that does not also hold lane 0)
   if constexpr (!EXIT) if (pair_lane) { off0 = cell_start[c0]; end0 = cell_start[c0 + 1]; off1 = cell_start[c1]; end1 = cell_start[c1 + 1]; }
   if constexpr (SKIP && !EXIT) {
-    coal_skip_fetch<T>(sk, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
+    coal_skip_fetch<T>(sk, tile, pair_lane, c0, c1, dv, kc.r_max, emax_l, ska);
     if (int(t) < ska.n_emax) emax_l[t] = ska.emax[t];           // (n_emax <= EMAX_CAP = BS: the host launches this form only then)
   }
 #pragma unroll
@@ -2883,16 +2891,84 @@ k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, con
   }
   __syncthreads();
   if constexpr (EXIT) {
-    if (!kept) return;
+    if (!kept) return true;
     const uint32_t s = own.shift ? 1u : 0u;
     coal_collide<T, false, TALLY>(own, ids[2 * t + s], ids[2 * t + s + 1], scl, true, u_pre, dvc_pre, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr,
                                   (T *)nullptr, (T *)nullptr, ijk_mark, ta);
-    return;
+    return true;
   }
-  if (!pair_lane) return;
+  if (!pair_lane) return true;
   const uint32_t i0 = ids[2 * t], i1 = ids[2 * t + 1], i2 = has2 ? ids[2 * t + 2] : 0u;
   coal_pair<T, false, TALLY>(p0, has2, c0, c1, c2, i0, i1, i2, off0, end0, off1, end1, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr, (T *)nullptr,
                              (T *)nullptr, ijk_mark, SKIP ? &sk : (const coal_skip<T> *)nullptr, ta);
+  return true;
+}
+// The kernel: one tile per workgroup -- or, where the cells have voted ahead of the launch (ska.flags, round 10), COAL_TILES_PER_WG tiles in turn: a
+// launch of one workgroup per tile took 0.46 ms on the 128^3 x 64 box with most of its 2.6e5 workgroups returning on their flag (12.5 KB of LDS and
+// 80 VGPRs allotted to each before its first instruction; EXPERIMENTS.md 7.13).  Kept tiles are few and scattered, so a workgroup finds about one.
+// TILES is that form, a kernel of its own (the host sizes the grid to match): the loop costs registers (123 VGPRs against 80), which the one-tile forms
+// do not pay.
+constexpr uint32_t COAL_TILES_PER_WG = 8;
+template <class T, bool MARK, bool SKIP = false, bool EXIT = false, bool TALLY = false, bool TILES = false>
+__global__ void __launch_bounds__(BS)
+k_coal_ranked(size_t n_part, const uint32_t *in, const uint32_t *sorted_ijk, const uint32_t *cell_start, rng_src r,
+              n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_skip_args<T> ska = {},
+              coal_tally_arg<T, TALLY> ta = {})
+{
+  static_assert(EXIT || !TILES, "the tiles' flags are the exit's");
+  if constexpr (TILES) {
+    constexpr uint32_t per = COAL_TILES_PER_WG;
+    bool ran = false;
+#pragma unroll 1
+    for (uint32_t k = 0; k < per; ++k) {
+      if (size_t(blockIdx.x * per + k) * COAL_RANKED_POS >= n_part) break;   // (behind the last tile; uniform)
+      if (ran) __syncthreads();                                            // (the last tile's lanes may still be reading its ranked ids)
+      if (coal_ranked_tile<T, MARK, SKIP, EXIT, TALLY>(blockIdx.x * per + k, n_part, in, sorted_ijk, cell_start, r, n, rw2, vt, rd3, dv, dt, kc, rs, ijk_mark, ska, ta)) ran = true;
+    }
+  }
+  else coal_ranked_tile<T, MARK, SKIP, EXIT, TALLY>(blockIdx.x, n_part, in, sorted_ijk, cell_start, r, n, rw2, vt, rd3, dv, dt, kc, rs, ijk_mark, ska, ta);
+}
+// Round 10: THE CELLS VOTE AHEAD OF THE LAUNCH (lcx_coal_prevote.hpp; EXPERIMENTS.md 7.13).  The leaving path of the EXIT form was bound by the vector
+// ALU: a Philox draw per pair (40 quarter-rate multiplies), the bound's divisions and square root per lane, 286 instructions per wave at 0.83 of the
+// ALU's cycles.  Neither depends on the pair beyond its cell and its position.
+// k_coal_umin: the smallest draw of every cell's pairs, from cell_start, the call number and the seed alone -- no per-droplet array is read.  It runs on
+// the side stream beside the velocity pass (lcx_core.hip step_async), which waits for memory.  Eight lanes per cell take every eighth pair.
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_coal_umin(size_t n_cell, const uint32_t *cell_start, uint64_t call, uint64_t seed, T *umin)
+{
+  constexpr unsigned L = 8;
+  const size_t g = gid(), c = g / L;
+  const unsigned sub = unsigned(g % L);
+  T m = T(__builtin_huge_valf());
+  if (c < n_cell) m = coal_cell_umin<T>(cell_start[c], cell_start[c + 1], call, seed, sub, L);
+#pragma unroll
+  for (unsigned d = 1; d < L; d <<= 1) { const T o = __shfl_xor(m, int(d)); if (o < m) m = o; }
+  if (c < n_cell && sub == 0) umin[c] = m;
+}
+// k_coal_cellvote: one lane per cell, behind the velocity pass that left the cell's maxima.  The cell holds a kept pair iff
+// !(bound < 1 && umin >= bound); where it does, the flags of the tiles its stretch overlaps are set (plain stores of 1 into an array cleared on the
+// stream; coal_cell_tiles says why those tiles are enough).
+// The vote may only err toward keeping.  umin is exact: integer arithmetic and a minimum, the same draws the lanes make.  The bound is coal_bound of
+// the very numbers a lane of the coalescence kernel is handed, times 1 + 2^-10 here: were the two kernels' roundings ever to differ (a dozen
+// operations of relative error <= 2^-23 each), the lane's bound is still below this one, so `this bound < 1 && umin >= this bound` implies
+// `lane's bound < 1 && u >= lane's bound` for every pair of the cell -- a tile is only flagged off where every lane would have skipped.  A flagged tile
+// is decided again by its own lanes, so the margin costs nothing.  A NaN bound (a poisoned cell, an infinite maximum, a cell within 11 um of the
+// table's end) fails the comparison and keeps the cell.  A cell without a pair keeps nothing.
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_coal_cellvote(size_t n_cell, const uint32_t *cell_start, const uint32_t *cmax, const T *dv, const T *umin, const n_t *n_max, const T *emax, int n_emax,
+                T r_max, T dt, uint32_t *flags, uint64_t n_tiles)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  const uint32_t off = cell_start[c], end = cell_start[c + 1];
+  if (end - off < 2u) return;
+  struct alignas(8) pairU { uint32_t a, b; };
+  const pairU m = *reinterpret_cast<const pairU *>(cmax + 2 * c);
+  const T bound = coal_bound<T>(m.a, m.b, dv[c], coal_scale_of<T>(n_t(end - off)), dt, T(*n_max), r_max, emax, n_emax) * T(1 + 1. / 1024);
+  if (bound < T(1) && umin[c] >= bound) return;
+  const coal_tile_range r = coal_cell_tiles(off, end, COAL_RANKED_POS);
+  for (uint64_t k = r.first; k <= r.last && k < n_tiles; ++k) flags[k] = 1u;                 // (every position lies below n_part: k < n_tiles holds)
 }
 // weighted_summator, coal.ipp:57-97,458-480 (only with more than one kappa in the run)
 template <class T>

@@ -131,6 +131,7 @@ class dbg2(enum.IntFlag):
     COAL_SKIP_COUNT = 1 << 0
     NO_COAL_RANK_EXIT = 1 << 1
     COAL_RANK_EXIT_ALWAYS = 1 << 2
+    NO_COAL_PREVOTE = 1 << 3
 
 
 class cond_kernel(enum.IntEnum):

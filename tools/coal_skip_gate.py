@@ -18,6 +18,13 @@ droplet shrunk like that except those of the cells with index % K == R, which be
 multiplicity 2.5e9 -- in the natural spectrum a kept pair collides once in two thousand times (the bound takes the box's largest
 multiplicity and the cell's largest radius and velocity); here one in six does, so that at K = 8 a group of 512 positions holds ONE cell
 whose one or two kept pairs often collide (the same test file's sparse box: --workload coal-stress --dt 0.05 --sparse 8:2 --steps 1,2,5,10).
+
+--prevote: for the cells' vote ahead of the launch (k_coal_umin, k_coal_cellvote; EXPERIMENTS.md 7.13) the "radius" row also gives, side by side,
+the share of the groups flagged through their cells -- every group that the stretch of a cell with a kept pair overlaps -- and the share of
+the groups that hold a kept pair themselves: what the per-cell granularity costs (--steps 5,50,100,200 for the headline's table).
+
+A step in which no pair is kept (the stratocumulus box's first) prints its rows up to the groups' shares and not the line of kept pairs
+per group, with or without --prevote: there is nothing to average (that line used to end the run with numpy's error on an empty maximum).
 """
 import argparse
 import os
@@ -75,7 +82,7 @@ def float_up(x):
     return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float64)
 
 
-def gate(orc, oi, tab, r_max, emax, rng, label, group=512):
+def gate(orc, oi, tab, r_max, emax, rng, label, group=512, prevote=False):
     n, rw2, vt, ijk = orc.state_u64("n").astype(np.float64), orc.get_attr("rw2"), orc.state_real("vt"), orc.state_u64("ijk").astype(np.int64)
     ncell = oi.nx * oi.ny * oi.nz
     dv = oi.dx * oi.dy * oi.dz
@@ -117,6 +124,18 @@ def gate(orc, oi, tab, r_max, emax, rng, label, group=512):
             print("         groups of %d positions with a kept pair %.4f (%d of %d), cells with a kept pair %.4f, pairs that collide %d"
                   % (group, len(groups) / ((len(c) + group - 1) // group), len(groups), (len(c) + group - 1) // group,
                      len(np.unique(cell[kept])) / ncell, int((u < prob).sum())))
+            if prevote:
+                # the cells' vote: a cell is kept iff it holds a kept pair (the bound is the cell's, so that is `not (bound_c < 1 and umin_c >=
+                # bound_c)` with umin_c the smallest draw of its pairs) or its bound is NaN; a kept cell flags every group its stretch overlaps
+                kc = np.union1d(np.unique(cell[kept]), np.nonzero(np.isnan(e) & (cnt >= 2))[0])
+                flagged = np.zeros((len(c) + group - 1) // group, dtype=bool)
+                for t0, t1 in zip(start[kc] // group, (start[kc + 1] - 1) // group):
+                    flagged[t0:t1 + 1] = True
+                assert flagged[groups].all()                 # (the vote only errs toward keeping)
+                print("         prevote: groups flagged through their cells %.4f (%d)  |  groups that hold a kept pair %.4f (%d)  |  flagged off %.4f"
+                      % (flagged.mean(), flagged.sum(), len(groups) / len(flagged), len(groups), 1 - flagged.mean()))
+            if not kept.any():
+                continue
             per_group = np.bincount(pa[kept] // group)
             print("         kept pairs in a group that has any: mean %.2f, most %d; bound of the kept pairs' cells: median %.3g, below 1: %.3f"
                   % (per_group[per_group > 0].mean(), per_group.max(), np.median(bound[kept]), (bound[kept] < 1).mean()))
@@ -132,6 +151,7 @@ def main():
     ap.add_argument("--group", type=int, default=512)
     ap.add_argument("--mixed", action="store_true")
     ap.add_argument("--sparse", default=None, metavar="K:R")
+    ap.add_argument("--prevote", action="store_true")
     args = ap.parse_args()
     at = sorted(int(s) for s in args.steps.split(","))
     n = args.n
@@ -167,7 +187,7 @@ def main():
                 x, y, z = orc.get_attr("x"), orc.get_attr("y"), orc.get_attr("z")
                 mine = ((x // oi.dx).astype(np.int64) * oi.ny + (y // oi.dy).astype(np.int64)) * oi.nz + (z // oi.dz).astype(np.int64)
                 assert np.array_equal(mine, orc.state_u64("ijk").astype(np.int64))
-            gate(orc, oi, tab, r_max, emax, rng, "step %d" % step, args.group)
+            gate(orc, oi, tab, r_max, emax, rng, "step %d" % step, args.group, args.prevote)
         orc.step_async(opts)
 
 
