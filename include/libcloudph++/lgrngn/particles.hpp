@@ -19,6 +19,7 @@
 #include "../../lcx_diag.h"
 #include "../../lcx_coal_rates.h"
 #include "../../lcx_cond_rates.h"
+#include "../../lcx_move_rates.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -107,6 +108,14 @@ namespace libcloudphxx { namespace lgrngn {
     diag_req_t &dry_mom(int k_) { count = LCX_DIAG_DRY_MOM; k = k_; return *this; }
     diag_req_t &wet_mom(int k_) { count = LCX_DIAG_WET_MOM; k = k_; return *this; }
     diag_req_t &kappa_mom(int k_) { count = LCX_DIAG_KAPPA_MOM; k = k_; return *this; }
+  };
+
+  // the rows of one threshold of particles_t<real_t, HIP>::move_rates (an extension without a reference counterpart; include/lcx_move_rates.h
+  // defines each of them)
+  enum class move_rate_t : int
+  {
+    in_n = LCX_MVR_IN_N, in_m3 = LCX_MVR_IN_M3, out_n = LCX_MVR_OUT_N, out_m3 = LCX_MVR_OUT_M3, down_n = LCX_MVR_DOWN_N, down_m3 = LCX_MVR_DOWN_M3,
+    up_n = LCX_MVR_UP_N, up_m3 = LCX_MVR_UP_M3, precip_n = LCX_MVR_PRECIP_N, precip_m3 = LCX_MVR_PRECIP_M3, per_thr = LCX_MVR_PER_THR
   };
 
   // the rows of one threshold of particles_t<real_t, HIP>::cond_rates (an extension without a reference counterpart; include/lcx_cond_rates.h
@@ -407,6 +416,32 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_cond_rates_info(pimpl->h, nullptr, &n_thr, nullptr, nullptr));
       detail::lcx_check(lcx_diag_cond_rate(pimpl->h, which == cond_rate_t::total_dm3 ? LCX_CDR_PER_THR * n_thr : LCX_CDR_PER_THR * t + int(which)));
     }
+    // EXTENSION, no reference counterpart (include/lcx_move_rates.h): per-cell tally of what step_async's move carries into and out of a cell, down
+    // and up through its levels and onto the ground, relative to up to LCX_MVR_MAX_THR increasing threshold radii (the first may be 0: every
+    // droplet), filled by a pass of its own around the move while enabled.  move_rates: out[row * n_cell + cell] with row = 10 t + int(move_rate_t)
+    // (resized to 10 K * n_cell), the numbers as doubles; reset zeroes the rows behind the read.  diag_move_rate fills outbuf() like a diag_*_mom
+    // call.  A snapshot does not hold them: a restored object is disabled.  Not virtual, as above.
+    void move_rates_enable(const std::vector<real_t> &r_thr)
+    {
+      std::vector<double> r(r_thr.begin(), r_thr.end());
+      detail::lcx_check(lcx_move_rates_enable(pimpl->h, r.data(), int(r.size())));
+    }
+    void move_rates_disable() { detail::lcx_check(lcx_move_rates_disable(pimpl->h)); }
+    unsigned long long move_rates_calls()
+    {
+      unsigned long long calls = 0;
+      detail::lcx_check(lcx_move_rates_info(pimpl->h, nullptr, nullptr, nullptr, &calls));
+      return calls;
+    }
+    void move_rates(std::vector<double> &out, bool reset = false)
+    {
+      size_t n_cell = 0; int n_thr = 0;
+      detail::lcx_check(lcx_n_cell(pimpl->h, &n_cell));
+      detail::lcx_check(lcx_move_rates_info(pimpl->h, nullptr, &n_thr, nullptr, nullptr));
+      out.resize(size_t(LCX_MVR_PER_THR * n_thr) * n_cell);
+      detail::lcx_check(lcx_move_rates_read(pimpl->h, out.data(), n_cell, 0, reset ? 1 : 0));
+    }
+    void diag_move_rate(move_rate_t which, int t = 0) { detail::lcx_check(lcx_diag_move_rate(pimpl->h, LCX_MVR_PER_THR * t + int(which))); }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

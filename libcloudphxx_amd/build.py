@@ -17,7 +17,8 @@ DEPS = ["lcx_core.hip", "lcx_cond_wq.hip", "lcx_cond_wq.hpp", "lcx_kernels.hpp",
         os.path.join("..", "..", "include", "lcx.h"), os.path.join("..", "..", "include", "lcx_rlx.h"),
         os.path.join("..", "..", "include", "lcx_chem.h"), os.path.join("..", "..", "include", "lcx_state.h"),
         os.path.join("..", "..", "include", "lcx_diag.h"), os.path.join("..", "..", "include", "lcx_coal_rates.h"),
-        os.path.join("..", "..", "include", "lcx_cond_rates.h")]
+        os.path.join("..", "..", "include", "lcx_cond_rates.h"),
+        os.path.join("..", "..", "include", "lcx_move_rates.h")]
 
 
 def needs_build():

@@ -29,6 +29,7 @@
 #include "../../include/lcx_diag.h"
 #include "../../include/lcx_coal_rates.h"
 #include "../../include/lcx_cond_rates.h"
+#include "../../include/lcx_move_rates.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -151,6 +152,13 @@ struct IParticles {
   virtual void cond_rates_info(int *, int *, double *, unsigned long long *) { no_cond_rates(); }
   virtual void cond_rates_read(double *, size_t, bool, bool) { no_cond_rates(); }
   virtual void diag_cond_rate(int) { no_cond_rates(); }
+  // move rates per cell (include/lcx_move_rates.h): built for a single-device object
+  [[noreturn]] static void no_move_rates() { throw std::runtime_error("libcloudph++: move_rates on a multi-device object is not built"); }
+  virtual void move_rates_enable(const double *, int) { no_move_rates(); }
+  virtual void move_rates_disable() { no_move_rates(); }
+  virtual void move_rates_info(int *, int *, double *, unsigned long long *) { no_move_rates(); }
+  virtual void move_rates_read(double *, size_t, bool, bool) { no_move_rates(); }
+  virtual void diag_move_rate(int) { no_move_rates(); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -1904,6 +1912,97 @@ struct Particles : IParticles {
     Range r(this, "cond_rates");
     switch (cdr_k) { case 1: cdr_launch<1>(); break; case 2: cdr_launch<2>(); break; case 3: cdr_launch<3>(); break; default: cdr_launch<4>(); }
   }
+  // ---- move rates per cell (include/lcx_move_rates.h): 10 K rows per cell, fed by a pass of its own around step_async's move ----
+  // While they are on, step_async copies ijk and n into two scratch columns ahead of the move (mvr_before: the fused move overwrites ijk in
+  // place and every move zeroes the n of what it removes) and launches k_move_rates right behind it (mvr_tally), ahead of everything that
+  // appends, compacts, re-orders or re-indexes: one launch more, and no k_move instantiation is another one.  Off, nothing below is looked
+  // at and nothing is allocated.
+  bool mvr_on = false; int mvr_k = 0; double mvr_r_thr[LCX_MVR_MAX_THR] = {0, 0, 0, 0}; unsigned long long mvr_calls = 0;
+  DevBuf<unsigned long long> mvr_acc; DevBuf<uint32_t> mvr_ijk_before; DevBuf<n_t> mvr_n_before; DevBuf<double> mvr_out; std::vector<double> mvr_host;
+  int mvr_rows() const { return LCX_MVR_PER_THR * mvr_k; }
+  void mvr_zero() { HIPCHK(hipMemsetAsync(mvr_acc.p, 0, size_t(mvr_rows()) * ncell * sizeof(unsigned long long), st)); mvr_calls = 0; }
+  void move_rates_enable(const double *r_thr, int n_thr) override
+  {
+    if (distmem()) throw lcx_error("libcloudph++: move_rates on a decomposed domain is not built");
+    if (n_thr < 1 || n_thr > LCX_MVR_MAX_THR) throw lcx_error("libcloudph++: move_rates: n_thr = " + std::to_string(n_thr) + " is outside 1 .. " + std::to_string(int(LCX_MVR_MAX_THR)));
+    if (!r_thr) throw lcx_error("libcloudph++: move_rates: r_thr == NULL");
+    T lo_prev = T(0);
+    for (int t = 0; t < n_thr; ++t) {
+      if (!(r_thr[t] >= 0) || !std::isfinite(r_thr[t])) throw lcx_error("libcloudph++: move_rates: every threshold must be non-negative and finite");
+      if (t && !(r_thr[t] > r_thr[t - 1])) throw lcx_error("libcloudph++: move_rates: the thresholds must be strictly increasing");
+      double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, r_thr[t], r_thr[t], lo, hi);
+      if (t && !(T(lo) > lo_prev)) throw lcx_error("libcloudph++: move_rates: the bounds r_thr^2 of thresholds " + std::to_string(t - 1) + " and " + std::to_string(t) +
+                                                  " are not strictly increasing in the object's real type");
+      lo_prev = T(lo);
+    }
+    if (mvr_acc.p) HIPCHK(hipStreamSynchronize(st));             // (a kernel still queued may read the rows that a larger K re-allocates)
+    mvr_k = n_thr; for (int t = 0; t < LCX_MVR_MAX_THR; ++t) mvr_r_thr[t] = t < n_thr ? r_thr[t] : 0.;
+    mvr_acc.alloc(size_t(mvr_rows()) * ncell);
+    mvr_on = true;
+    mvr_zero();
+  }
+  void move_rates_disable() override
+  {
+    mvr_on = false; mvr_k = 0; mvr_calls = 0; for (double &r : mvr_r_thr) r = 0;
+    if (mvr_acc.p || mvr_ijk_before.p) { HIPCHK(hipStreamSynchronize(st)); mvr_acc.release(); mvr_ijk_before.release(); mvr_n_before.release(); mvr_out.release(); }
+  }
+  void move_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override
+  {
+    if (enabled) *enabled = mvr_on ? 1 : 0;
+    if (n_thr) *n_thr = mvr_k;
+    if (r_thr) for (int t = 0; t < mvr_k; ++t) r_thr[t] = mvr_r_thr[t];
+    if (calls) *calls = mvr_calls;
+  }
+  void mvr_need(const char *what) const { if (!mvr_on) throw lcx_error(std::string("libcloudph++: move_rates: ") + what + " while the tally is not enabled (lcx_move_rates_enable)"); }
+  void move_rates_read(double *out, size_t stride, bool on_device, bool reset) override
+  {
+    mvr_need("read");
+    if (!out) throw lcx_error("libcloudph++: move_rates: out == NULL");
+    if (stride < ncell) throw lcx_error("libcloudph++: move_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
+    const int rows = mvr_rows();
+    const dim3 gr(nblk(ncell), rows);
+    if (on_device) hipLaunchKernelGGL(k_move_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)mvr_acc.p, out, stride);
+    else {
+      mvr_out.alloc(size_t(rows) * ncell); mvr_host.resize(size_t(rows) * ncell);
+      hipLaunchKernelGGL(k_move_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)mvr_acc.p, mvr_out.p, ncell);
+      HIPCHK(hipMemcpyAsync(mvr_host.data(), mvr_out.p, mvr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (reset) mvr_zero();
+    sync();
+    if (!on_device) for (int w = 0; w < rows; ++w) memcpy(out + size_t(w) * stride, mvr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
+  }
+  void diag_move_rate(int row) override
+  {
+    mvr_need("diag_move_rate");
+    if (!init_called) throw lcx_error("libcloudph++: move_rates: diag_move_rate before init()");
+    if (row < 0 || row >= mvr_rows()) throw lcx_error("libcloudph++: move_rates: row = " + std::to_string(row) + " is outside 0 .. " + std::to_string(mvr_rows() - 1));
+    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(mvr_acc.p + size_t(row) * ncell),
+                       row & 1, (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
+    sync();
+  }
+  // step_async, ahead of the move: ijk and n as stored, into the scratch columns (allocated here: the capacity is not known before init)
+  void mvr_before()
+  {
+    if (!nphys || n_dims == 0) return;
+    if (mvr_ijk_before.n < A.n.n) { HIPCHK(hipStreamSynchronize(st)); mvr_ijk_before.alloc(A.n.n); mvr_n_before.alloc(A.n.n); }   // (first use, or the storage has grown)
+    HIPCHK(hipMemcpyAsync(mvr_ijk_before.p, ijk.p, nphys * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(mvr_n_before.p, A.n.p, nphys * sizeof(n_t), hipMemcpyDeviceToDevice, st));
+  }
+  // step_async, right behind the move (n_moved: the slots that the move saw; fused: ijk holds the new cells)
+  template <int K> void mvr_launch(size_t n_moved, bool fused)
+  {
+    move_rates_arg<T, K> a{mvr_n_before.p, A.n.p, mvr_ijk_before.p, fused ? (const uint32_t *)ijk.p : (const uint32_t *)nullptr, A.rw2.p, A.x.p, A.y.p, A.z.p,
+                           mvr_acc.p, ncell, g, T(o.x0), T(o.x1), T(o.y0), T(o.y1), T(o.z0), T(o.z1), int(o.open_side_walls), int(o.periodic_topbot_walls), {}};
+    for (int t = 0; t < K; ++t) { double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, mvr_r_thr[t], mvr_r_thr[t], lo, hi); a.lo[t] = T(lo); }
+    hipLaunchKernelGGL((k_move_rates<T, K>), dim3(nblk(n_moved)), dim3(BS), 0, st, n_moved, a);
+  }
+  void mvr_tally(size_t n_moved, bool fused)
+  {
+    ++mvr_calls;
+    if (!n_moved || n_dims == 0) return;
+    Range r(this, "move_rates");
+    switch (mvr_k) { case 1: mvr_launch<1>(n_moved, fused); break; case 2: mvr_launch<2>(n_moved, fused); break; case 3: mvr_launch<3>(n_moved, fused); break; default: mvr_launch<4>(n_moved, fused); }
+  }
   void refresh_n_max()
   {
     if (!n_max_stale) return;
@@ -2939,7 +3038,10 @@ struct Particles : IParticles {
     // an order still owed: void where the step ends in the fused move and its re-sort with nothing in between that reads the old order (the
     // move writes the next sort's arrival ranks); made now otherwise
     if (rank_owed) { if (fused && !distmem() && !src_now && !rlx_now) rank_owed = false; else pay_rank(); }
+    if (mvr_on) mvr_before();                      // (include/lcx_move_rates.h: ijk and n as stored ahead of the move)
+    const size_t n_moved = nphys;
     move(opts.adve, opts.sedi, opts.subs, true, fused);
+    if (mvr_on) mvr_tally(n_moved, fused);         // (ahead of whatever appends, compacts, re-orders or re-indexes)
     if (n_chem_pud) chem_puddle_add(n_chem_pud);
     hold_big_list = false;
     adve_scheme = o.adve_scheme;
@@ -3969,6 +4071,7 @@ struct Particles : IParticles {
       sync();
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)
+      move_rates_disable();                        // (include/lcx_move_rates.h: the same)
     } catch (...) { roll_back(); throw; }
   }
   // what the constructor left zero and a load that failed half-way may have written
@@ -4248,6 +4351,13 @@ int lcx_coal_rates_info(lcx_particles *h, int *enabled, double *r_thr, unsigned 
 int lcx_coal_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
 { LCX_TRY(H->coal_rates_read(out, stride, out_on_device != 0, reset != 0)) }
 int lcx_diag_coal_rate(lcx_particles *h, int which) { LCX_TRY(H->diag_coal_rate(which)) }
+// ---- move rates per cell (include/lcx_move_rates.h) ----
+int lcx_move_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->move_rates_enable(r_thr, n_thr)) }
+int lcx_move_rates_disable(lcx_particles *h) { LCX_TRY(H->move_rates_disable()) }
+int lcx_move_rates_info(lcx_particles *h, int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) { LCX_TRY(H->move_rates_info(enabled, n_thr, r_thr, calls)) }
+int lcx_move_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
+{ LCX_TRY(H->move_rates_read(out, stride, out_on_device != 0, reset != 0)) }
+int lcx_diag_move_rate(lcx_particles *h, int row) { LCX_TRY(H->diag_move_rate(row)) }
 // ---- condensation rates per cell (include/lcx_cond_rates.h) ----
 int lcx_cond_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->cond_rates_enable(r_thr, n_thr)) }
 int lcx_cond_rates_disable(lcx_particles *h) { LCX_TRY(H->cond_rates_disable()) }

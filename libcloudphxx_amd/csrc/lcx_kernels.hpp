@@ -3077,6 +3077,133 @@ __global__ void k_cond_rates_f64(size_t n_cell, const unsigned long long *acc, i
   out[size_t(w) * stride + c] = is_n ? double(row[c]) : reinterpret_cast<const double *>(row)[c];
 }
 
+// Move rates (include/lcx_move_rates.h): what the one move of a step_async did to every droplet relative to K thresholds, from
+// ijk and n as they were ahead of the move (ijk_0, n_0: the scratch columns) and as they are now.  acc is [10 K][n_cell] words of 8 bytes: even rows
+// (_N) hold unsigned 64-bit integers, odd rows (_M3) doubles.  A slot per lane in storage order, nothing gathered.  The new cell is the ijk that the
+// fused move stored (ijk_1), or, behind a plain move (ijk_1 == nullptr), cell_of() of the stored position: what the later re-indexing computes.
+// Every family of rows -- OUT, DOWN and UP at c0, IN at c1, PRECIP at the foot of c0's column -- goes through mvr_add: the lanes that feed it are
+// grouped by target cell with ballots (as wave_hist_rank does; adjacent or not), ALL groups are summed at once by a tree over each lane's peers
+// (log2 of the largest group rounds, a fixed order for a given wave), and each group's first lane issues one atomic per row.  A family that no lane
+// of the wave feeds costs one ballot.  (The first form summed OUT / DOWN / UP along runs of adjacent lanes and every IN group by a butterfly over
+// the whole wave, a group at a time: EXPERIMENTS.md 7.14 has both.)  Every target is checked against n_cell before anything is added.  Any storage
+// order is correct; the integer sums do not depend on it.
+template <class T, int K> struct move_rates_arg {
+  const n_t *n_0, *n_1; const uint32_t *ijk_0, *ijk_1; const T *rw2, *x, *y, *z; unsigned long long *acc; size_t n_cell; grid_t g;
+  T x0, x1, y0, y1, z0, z1; int open_side_walls, periodic_topbot; T lo[K];
+};
+// the mask of the active lanes that share this lane's target (0 for a lane that is not active); every lane of the wave calls it
+__device__ __forceinline__ unsigned long long mvr_peers(uint32_t tgt, bool active)
+{
+  const unsigned l = lane_id();
+  unsigned long long todo = __ballot(active), mine = 0ull;
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const uint32_t lc = __shfl(tgt, leader);
+    const unsigned long long same = __ballot(active && tgt == lc);
+    if ((same >> l) & 1ull) mine = same;
+    todo &= ~same;
+  }
+  return mine;
+}
+// One family of rows: n[t] = mu and m[t] = mr3 for the thresholds t < kt that the droplet is above, summed over the lanes of equal target and added
+// to rows 10 t + which (numbers) and 10 t + which + 1 (m r^3) of that cell by the group's first lane.  The tree: in every round a lane adds the
+// value of the next peer above it, the peers of odd rank drop out and the ranks halve; the sum ends in the peer of rank 0.
+template <int K>
+__device__ __forceinline__ void mvr_add(unsigned long long *acc, size_t nc, int which, uint32_t tgt, bool active, int kt, unsigned long long mu, double mr3)
+{
+  active = active && size_t(tgt) < nc && kt > 0;
+  if (!__ballot(active)) return;
+  const unsigned l = lane_id();
+  const unsigned long long peers = mvr_peers(tgt, active);
+  unsigned long long n[K]; double m[K]; bool fed[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) { const bool on = active && t < kt; n[t] = on ? mu : 0ull; m[t] = on ? mr3 : 0.; fed[t] = __ballot(on) != 0ull; }
+  unsigned rel = unsigned(__popcll(peers & ((1ull << l) - 1ull)));
+  const bool first = active && rel == 0;
+  unsigned long long above = l == WAVE - 1 ? 0ull : peers & ~((2ull << l) - 1ull);       // the peers in higher lanes
+  while (__ballot(above != 0ull)) {
+    const bool has = above != 0ull;
+    const int next = has ? __ffsll((long long)above) - 1 : int(l);
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+      if (fed[t]) {
+        const unsigned long long tn = __shfl(n[t], next); const double tm = __shfl(m[t], next);
+        if (has) { n[t] += tn; m[t] += tm; }
+      }
+    above &= __ballot(!(rel & 1u));                                     // (the odd ranks have been taken in by their left peers)
+    rel >>= 1;
+  }
+  if (first) {
+    unsigned long long *row = acc + tgt;
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+      if (n[t]) {
+        atomicAdd(row + size_t(LCX_MVR_PER_THR * t + which) * nc, n[t]);
+        if (m[t] != 0.) unsafeAtomicAdd(reinterpret_cast<double *>(row + size_t(LCX_MVR_PER_THR * t + which + 1) * nc), m[t]);
+      }
+  }
+}
+template <class T, int K>
+__global__ void __launch_bounds__(BS) k_move_rates(size_t n_part, const move_rates_arg<T, K> a)
+{
+  const size_t i = gid();
+  const grid_t &g = a.g;
+  uint32_t c0 = DEAD_CELL, c1 = DEAD_CELL, cp = DEAD_CELL; unsigned long long mu = 0ull; double mr3 = 0.; T rw2 = T(0);
+  bool moved = false, down = false, up = false;
+  if (i < n_part) {
+    const uint32_t ci = a.ijk_0[i];
+    if (size_t(ci) < a.n_cell) {
+      c0 = ci;
+      // what every slot costs is its two cells (behind a fused move; the fused move stores DEAD_CELL for what it removes, and that alone): rw2 is
+      // read of those that left their cell, and n_0 of those that are above the first threshold as well
+      bool removed; uint32_t cn = DEAD_CELL;
+      if (a.ijk_1) { cn = a.ijk_1[i]; removed = cn == DEAD_CELL; }
+      else { removed = a.n_1[i] == 0; if (!removed) cn = cell_of(g, g.nx ? a.x[i] : T(0), g.ny ? a.y[i] : T(0), g.nz ? a.z[i] : T(0)); }
+      if (removed || cn != ci) {
+        rw2 = a.rw2[i];
+        const n_t mult = rw2 >= a.lo[0] ? a.n_0[i] : n_t(0);            // (the thresholds increase: below the first is below all)
+        if (mult != 0) {                                                // (m == 0: a slot that was dead ahead of the move)
+          moved = true;
+          const uint32_t nz = g.ndims > 1 ? uint32_t(g.nz) : 1u, k0 = ci % nz;
+          if (!removed) {
+            c1 = cn;
+            if (g.ndims > 1 && size_t(c1) < a.n_cell) { const uint32_t k1 = c1 % nz; down = k1 < k0; up = k1 > k0; }
+          } else {
+            // the exit, in the order of k_move: side walls, then top, then bottom
+            bool side = false;
+            if (a.open_side_walls) {
+              if (g.nx) { const T x = a.x[i]; side = x >= a.x1 || x < a.x0; }
+              if (g.ndims == 3) { const T y = a.y[i]; side = side || y >= a.y1 || y < a.y0; }
+            }
+            if (!side && g.ndims > 1 && !a.periodic_topbot) {
+              const T z = a.z[i];
+              if (z >= a.z1) up = true; else if (z < a.z0) { down = true; cp = ci - k0; }
+            }
+          }
+          const double d = double(rw2); mu = (unsigned long long)mult; mr3 = double(mult) * (d * sqrt(d));
+        }
+      }
+    }
+  }
+  if (!__ballot(moved)) return;
+  int kt = 0;                                                           // the thresholds that the droplet is above (they increase)
+#pragma unroll
+  for (int t = 0; t < K; ++t) kt += moved && rw2 >= a.lo[t] ? 1 : 0;
+  mvr_add<K>(a.acc, a.n_cell, LCX_MVR_OUT_N, c0, moved, kt, mu, mr3);
+  mvr_add<K>(a.acc, a.n_cell, LCX_MVR_IN_N, c1, moved && c1 != DEAD_CELL, kt, mu, mr3);
+  mvr_add<K>(a.acc, a.n_cell, LCX_MVR_DOWN_N, c0, moved && down, kt, mu, mr3);
+  mvr_add<K>(a.acc, a.n_cell, LCX_MVR_UP_N, c0, moved && up, kt, mu, mr3);
+  mvr_add<K>(a.acc, a.n_cell, LCX_MVR_PRECIP_N, cp, moved && cp != DEAD_CELL, kt, mu, mr3);
+}
+// lcx_move_rates_read: the [10 K][n_cell] block as doubles (the even rows are numbers and converted), out[row * stride + c]
+__global__ void k_move_rates_f64(size_t n_cell, const unsigned long long *acc, double *out, size_t stride)
+{
+  const size_t c = gid(); if (c >= n_cell) return;
+  const unsigned w = blockIdx.y;
+  const unsigned long long *row = acc + size_t(w) * n_cell;
+  out[size_t(w) * stride + c] = w & 1u ? reinterpret_cast<const double *>(row)[c] : double(row[c]);
+}
+
 // ============================================================================================
 // advection + sedimentation + subsidence + boundary conditions in ONE pass
 // (adve.ipp:28-165,169-183; sedi.ipp:13-25; subs.ipp:13-25; bcnd.ipp:99-368)

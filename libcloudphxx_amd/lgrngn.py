@@ -419,6 +419,61 @@ def cond_rates_out(out, n_thr, n_cell):
     return ptr, strides[0], isinstance(out, DeviceArray)
 
 
+# ---- move rates per cell (include/lcx_move_rates.h)
+MOVE_RATES = ("in_n", "in_m3", "out_n", "out_m3", "down_n", "down_m3", "up_n", "up_m3", "precip_n", "precip_m3")   # enum LCX_MVR_*, in its order
+MOVE_RATES_MAX_THR = 4                                               # LCX_MVR_MAX_THR
+
+
+def move_rates_thresholds(r_thr):
+    """the thresholds as lcx_move_rates_enable takes them, from a scalar or a sequence: 1 .. 4 finite, strictly increasing radii, the first
+    may be 0 (every droplet)"""
+    r = [float(x) for x in np.atleast_1d(np.asarray(r_thr, dtype=np.float64)).ravel()]
+    if not 1 <= len(r) <= MOVE_RATES_MAX_THR:
+        raise ValueError("libcloudph++: move_rates: n_thr = %d is outside 1 .. %d" % (len(r), MOVE_RATES_MAX_THR))
+    if not all(x >= 0 and np.isfinite(x) for x in r):
+        raise ValueError("libcloudph++: move_rates: every threshold must be non-negative and finite")
+    if any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError("libcloudph++: move_rates: the thresholds must be strictly increasing")
+    return r
+
+
+def move_rate_index(name, t=0, n_thr=MOVE_RATES_MAX_THR):
+    """the row of a name of MOVE_RATES at threshold t, or of a row number, among 10 n_thr rows"""
+    n_rows = len(MOVE_RATES) * n_thr
+    if isinstance(name, str):
+        if name.lower() not in MOVE_RATES:
+            raise ValueError("libcloudph++: move_rates: unknown row %r (one of %s)" % (name, ", ".join(MOVE_RATES)))
+        t = int(t)
+        if not 0 <= t < n_thr:
+            raise ValueError("libcloudph++: move_rates: t = %d is outside 0 .. %d" % (t, n_thr - 1))
+        return len(MOVE_RATES) * t + MOVE_RATES.index(name.lower())
+    w = int(name)
+    if not 0 <= w < n_rows:
+        raise ValueError("libcloudph++: move_rates: row = %d is outside 0 .. %d" % (w, n_rows - 1))
+    return w
+
+
+def move_rates_out(out, n_thr, n_cell):
+    """(address, row stride in doubles, on_device) of an output array of move_rates: (10 n_thr, n_cell) doubles with unit stride along
+    cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
+    n_rows = len(MOVE_RATES) * n_thr
+    if len(out.shape) != 2 or out.shape[0] != n_rows or out.shape[1] != n_cell:
+        raise ValueError("libcloudph++: move_rates: out must be 2-D, (%d, n_cell)" % n_rows)
+    if isinstance(out, DeviceArray):
+        ptr, strides = out.ptr, out.strides
+    else:
+        if out.dtype != np.float64:
+            raise ValueError("libcloudph++: move_rates: out must hold float64")
+        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
+            raise ValueError("libcloudph++: move_rates: unsupported strides")
+        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
+    if n_cell > 1 and strides[1] != 1:
+        raise ValueError("libcloudph++: move_rates: out must have unit stride along cells")
+    if strides[0] < n_cell:
+        raise ValueError("libcloudph++: move_rates: out's row stride is below n_cell")
+    return ptr, strides[0], isinstance(out, DeviceArray)
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -977,6 +1032,39 @@ class particles_t:
         """fills outbuf() with one row (a name of COND_RATES at threshold t, "total_dm3", or a row number), normalised as a diag_*_mom result"""
         n_thr = max(len(self.cond_rates_info()[1]), 1)
         self._chk(self._f("diag_cond_rate")(self._h, C.c_int(cond_rate_index(name_or_row, t, n_thr))))
+
+    # -- move rates per cell (include/lcx_move_rates.h; no reference counterpart)
+    def move_rates_enable(self, r_thr):
+        """start (or restart from zero) the per-cell tally of what step_async's move carries in, out, up, down and onto the ground, relative
+        to the threshold radii r_thr (a scalar or up to four increasing values, the first may be 0); before or after init()"""
+        r = move_rates_thresholds(r_thr)
+        self._chk(self._f("move_rates_enable")(self._h, (C.c_double * len(r))(*r), C.c_int(len(r))))
+
+    def move_rates_disable(self):
+        self._chk(self._f("move_rates_disable")(self._h))
+
+    def move_rates_info(self):
+        """(enabled, the thresholds as a tuple, moves tallied since enable or the last reset)"""
+        en, k, r, n = C.c_int(), C.c_int(), (C.c_double * MOVE_RATES_MAX_THR)(), C.c_ulonglong()
+        self._chk(self._f("move_rates_info")(self._h, C.byref(en), C.byref(k), r, C.byref(n)))
+        return bool(en.value), tuple(r[t] for t in range(k.value)), n.value
+
+    def move_rates(self, reset=False, out=None):
+        """the rows: a dict name of MOVE_RATES -> (K, n_cell) float64; with out= (a (10 K, n_cell) float64 numpy array or DeviceArray of the
+        object's device) fills and returns that.  reset: zero them behind the read."""
+        n_cell, n_thr = self.n_cell, max(len(self.move_rates_info()[1]), 1)
+        n_per = len(MOVE_RATES)
+        arr = np.zeros((n_per * n_thr, n_cell), dtype=np.float64) if out is None else out
+        ptr, stride, on_device = move_rates_out(arr, n_thr, n_cell)
+        self._chk(self._f("move_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        if out is not None:
+            return out
+        return {nm: arr[w::n_per] for w, nm in enumerate(MOVE_RATES)}
+
+    def diag_move_rate(self, name_or_row, t=0):
+        """fills outbuf() with one row (a name of MOVE_RATES at threshold t, or a row number), normalised as a diag_*_mom result"""
+        n_thr = max(len(self.move_rates_info()[1]), 1)
+        self._chk(self._f("diag_move_rate")(self._h, C.c_int(move_rate_index(name_or_row, t, n_thr))))
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
