@@ -379,8 +379,8 @@ int lcx_real_kind(lcx_particles *, int *kind);
 int lcx_get_state_u64(lcx_particles *, const char *name, unsigned long long *out, size_t cap, size_t *n);
 /* real state not covered by get_attr: "vt","T","p","RH","eta","th","rv","rhod","dv","lambda_D","lambda_K",
  * "courant_x","courant_y","courant_z","vt_0" (as double whatever the real kind).
- * Names that begin with "raw_" ("raw_n","raw_ijk" as u64; "raw_rw2","raw_rd3","raw_kappa","raw_vt","raw_x","raw_y","raw_z","raw_tag" as
- * reals) return the STORAGE as it is -- its whole extent, dead slots (n == 0) included, nothing compacted or sorted on the way: reading
+ * Names that begin with "raw_" ("raw_n","raw_ijk" as u64; "raw_rw2","raw_rd3","raw_kappa","raw_vt","raw_x","raw_y","raw_z","raw_tag" and
+ * "raw_track" -- a tracked droplet's mark (the tracking header), empty while tracking is off -- as reals) return the STORAGE as it is -- its whole extent, dead slots (n == 0) included, nothing compacted or sorted on the way: reading
  * them does not disturb a production run, whereas every other particle-state getter first puts the storage into the reference's order.
  * "raw_collided" (u64, one value): living super-droplets that carry coalescence's invalid terminal velocity, i.e. the number of pairs that
  * collided in the last lcx_step_async (bench.py's coal-stress workload reports it).  "raw_sorted_id" (u64): the cell-sorted order as the

@@ -20,6 +20,7 @@
 #include "../../lcx_coal_rates.h"
 #include "../../lcx_cond_rates.h"
 #include "../../lcx_move_rates.h"
+#include "../../lcx_track.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -116,6 +117,22 @@ namespace libcloudphxx { namespace lgrngn {
   {
     in_n = LCX_MVR_IN_N, in_m3 = LCX_MVR_IN_M3, out_n = LCX_MVR_OUT_N, out_m3 = LCX_MVR_OUT_M3, down_n = LCX_MVR_DOWN_N, down_m3 = LCX_MVR_DOWN_M3,
     up_n = LCX_MVR_UP_N, up_m3 = LCX_MVR_UP_M3, precip_n = LCX_MVR_PRECIP_N, precip_m3 = LCX_MVR_PRECIP_M3, per_thr = LCX_MVR_PER_THR
+  };
+
+  // the fields of one record of particles_t<real_t, HIP>::track (an extension without a reference counterpart; include/lcx_track.h defines each)
+  enum track_field_t
+  {
+    trk_n = LCX_TRK_N, trk_x = LCX_TRK_X, trk_y = LCX_TRK_Y, trk_z = LCX_TRK_Z, trk_rw2 = LCX_TRK_RW2, trk_rd3 = LCX_TRK_RD3,
+    trk_kappa = LCX_TRK_KAPPA, trk_vt = LCX_TRK_VT, trk_cell = LCX_TRK_CELL, trk_T = LCX_TRK_T, trk_RH = LCX_TRK_RH, trk_rv = LCX_TRK_RV,
+    trk_fields = LCX_TRK_FIELDS
+  };
+  // what particles_t<real_t, HIP>::track reads: rec[(s * 12 + field) * n_tracked + k] for sample s and track index k
+  struct track_record_t
+  {
+    size_t n_samples = 0, n_tracked = 0;
+    std::vector<double> rec, time;
+    std::vector<unsigned long long> steps;
+    double at(size_t s, track_field_t f, size_t k) const { return rec[(s * size_t(LCX_TRK_FIELDS) + size_t(f)) * n_tracked + k]; }
   };
 
   // the rows of one threshold of particles_t<real_t, HIP>::cond_rates (an extension without a reference counterpart; include/lcx_cond_rates.h
@@ -442,6 +459,42 @@ namespace libcloudphxx { namespace lgrngn {
       detail::lcx_check(lcx_move_rates_read(pimpl->h, out.data(), n_cell, 0, reset ? 1 : 0));
     }
     void diag_move_rate(move_rate_t which, int t = 0) { detail::lcx_check(lcx_diag_move_rate(pimpl->h, LCX_MVR_PER_THR * t + int(which))); }
+    // EXTENSION, no reference counterpart (include/lcx_track.h): tracked super-droplets.  track_enable makes room for max_tracked droplets and
+    // `capacity` samples (every > 0: every every-th step_async ends in a sample); track_select marks droplets that satisfy every clause of
+    // `sel` (a diag_req_t's clauses, ANDed; its count is not read) and lie in box = {x0, x1, y0, y1, z0, z1} (empty: anywhere), at most
+    // max_count of them, spread over the storage, and returns how many it took; track_sample takes one sample now; track reads the samples
+    // held.  A snapshot does not hold the marks: a restored object is disabled.  Not virtual, as above.
+    void track_enable(size_t max_tracked, size_t capacity = 64, int every = 0) { detail::lcx_check(lcx_track_enable(pimpl->h, max_tracked, capacity, every)); }
+    void track_disable() { detail::lcx_check(lcx_track_disable(pimpl->h)); }
+    size_t track_select(const diag_req_t<real_t> &sel, const std::vector<double> &box = std::vector<double>(), size_t max_count = size_t(LCX_TRK_MAX))
+    {
+      std::vector<lcx_diag_clause_t> c;
+      for (const auto &cl : sel.clauses) c.push_back(lcx_diag_clause_t{cl.sel, double(cl.lo), double(cl.hi)});
+      if (!box.empty() && box.size() != 6) throw std::runtime_error("libcloudph++: track: box must hold six bounds (x0, x1, y0, y1, z0, z1)");
+      size_t got = 0;
+      detail::lcx_check(lcx_track_select(pimpl->h, c.data(), int(c.size()), box.empty() ? nullptr : box.data(), max_count, &got));
+      return got;
+    }
+    size_t track_select_slots(const std::vector<unsigned long long> &slots)
+    {
+      size_t got = 0;
+      detail::lcx_check(lcx_track_select_slots(pimpl->h, slots.data(), slots.size(), &got));
+      return got;
+    }
+    void track_sample() { detail::lcx_check(lcx_track_sample(pimpl->h)); }
+    // enabled, max_tracked, n_tracked, capacity, n_samples, dropped, every, scans: any pointer may be null
+    void track_info(int *enabled, size_t *max_tracked = nullptr, size_t *n_tracked = nullptr, size_t *capacity = nullptr, size_t *n_samples = nullptr,
+                    unsigned long long *dropped = nullptr, int *every = nullptr, unsigned long long *scans = nullptr)
+    { detail::lcx_check(lcx_track_info(pimpl->h, enabled, max_tracked, n_tracked, capacity, n_samples, dropped, every, scans)); }
+    void track(track_record_t &out, bool reset = false)
+    {
+      detail::lcx_check(lcx_track_info(pimpl->h, nullptr, nullptr, &out.n_tracked, nullptr, &out.n_samples, nullptr, nullptr, nullptr));
+      out.rec.assign(out.n_samples * size_t(LCX_TRK_FIELDS) * out.n_tracked, 0.);
+      out.steps.assign(out.n_samples, 0ull); out.time.assign(out.n_samples, 0.);
+      size_t got = 0;
+      detail::lcx_check(lcx_track_read(pimpl->h, out.rec.data(), size_t(LCX_TRK_FIELDS) * out.n_tracked, out.n_tracked, out.steps.data(), out.time.data(),
+                                       out.n_samples, &got, 0, reset ? 1 : 0));
+    }
 
   private:
     static lcx_opts_t conv(const opts_t<real_t> &o)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <algorithm>
+#include <unordered_set>
 #include <cmath>
 #include <limits>
 #include <cstdio>
@@ -30,6 +31,7 @@
 #include "../../include/lcx_coal_rates.h"
 #include "../../include/lcx_cond_rates.h"
 #include "../../include/lcx_move_rates.h"
+#include "../../include/lcx_track.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -159,6 +161,15 @@ struct IParticles {
   virtual void move_rates_info(int *, int *, double *, unsigned long long *) { no_move_rates(); }
   virtual void move_rates_read(double *, size_t, bool, bool) { no_move_rates(); }
   virtual void diag_move_rate(int) { no_move_rates(); }
+  // tracked super-droplets (include/lcx_track.h): built for a single-device object
+  [[noreturn]] static void no_track() { throw std::runtime_error("libcloudph++: track on a multi-device object is not built"); }
+  virtual void track_enable(size_t, size_t, int) { no_track(); }
+  virtual void track_disable() { no_track(); }
+  virtual void track_select(const lcx_diag_clause_t *, int, const double *, size_t, size_t *) { no_track(); }
+  virtual void track_select_slots(const unsigned long long *, size_t, size_t *) { no_track(); }
+  virtual void track_sample() { no_track(); }
+  virtual void track_info(int *, size_t *, size_t *, size_t *, size_t *, unsigned long long *, int *, unsigned long long *) { no_track(); }
+  virtual void track_read(double *, size_t, size_t, unsigned long long *, double *, size_t, size_t *, bool, bool) { no_track(); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -1262,6 +1273,10 @@ struct Particles : IParticles {
     HIPCHK(hipMemcpyAsync(rc_pairs.p, recv.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(rc_pairs.p + k, donor.data(), k * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rcyc_apply<T>, dim3(nblk(k)), dim3(BS), 0, st, k, rc_pairs.p, rc_pairs.p + k, aset(A), g);
+    if (ix_trk >= 0) {                             // (include/lcx_track.h: a receiver is a new droplet, the donor keeps its mark)
+      hipLaunchKernelGGL(k_track_unmark<T>, dim3(nblk(k)), dim3(BS), 0, st, k, (const uint32_t *)rc_pairs.p, A.ext[ix_trk].p);
+      trk_stale = true;
+    }
     sync();
   }
   DevBuf<unsigned int> rc_stat, rc_hist; DevBuf<unsigned long long> rc_max; DevBuf<n_t> rc_vals; DevBuf<uint32_t> rc_pairs;
@@ -1354,6 +1369,7 @@ struct Particles : IParticles {
   {
     A.n.swap(B.n); A.rd3.swap(B.rd3); A.rw2.swap(B.rw2); A.kpa.swap(B.kpa); A.vt.swap(B.vt); A.x.swap(B.x); A.y.swap(B.y); A.z.swap(B.z);
     for (int e = 0; e < n_ext; ++e) A.ext[e].swap(B.ext[e]);
+    trk_stale = true;                              // (include/lcx_track.h: compaction and re-ordering end here, the slots have moved)
   }
   // make storage order == the reference's (no dead SDs in it) before anything that exposes storage order
   void ensure_compact()
@@ -2003,6 +2019,183 @@ struct Particles : IParticles {
     Range r(this, "move_rates");
     switch (mvr_k) { case 1: mvr_launch<1>(n_moved, fused); break; case 2: mvr_launch<2>(n_moved, fused); break; case 3: mvr_launch<3>(n_moved, fused); break; default: mvr_launch<4>(n_moved, fused); }
   }
+  // ---- tracked super-droplets (include/lcx_track.h): one more ext column holding k + 1, the slot of every index, a sample buffer ----
+  // The column is the LAST one (nothing else adds columns after construction), so enabling and disabling are n_ext + 1 and n_ext - 1 and
+  // everything that carries ext[] generically -- k_compact, k_reorder, the swap of the two sets -- carries the mark.  No kernel choice reads
+  // n_ext.  trk_stale: slot_of must be found again (k_track_scan) before the next sample; set wherever storage is permuted or rewritten.
+  int ix_trk = -1, trk_every = 0; bool trk_stale = false;
+  size_t trk_max = 0, trk_n = 0, trk_cap = 0, trk_ns = 0;
+  unsigned long long trk_dropped = 0, trk_scans = 0, trk_step_count = 0; double trk_time_now = 0;
+  DevBuf<uint32_t> trk_slot_of, trk_part, trk_total, trk_ids; DevBuf<double> trk_buf, trk_out; DevBuf<unsigned long long> trk_slots_in; DevBuf<uint8_t> trk_ok;
+  std::vector<unsigned long long> trk_steps; std::vector<double> trk_times, trk_host;
+  void track_enable(size_t max_tracked, size_t capacity, int every) override
+  {
+    if (distmem()) throw lcx_error("libcloudph++: track on a decomposed domain is not built");
+    if (max_tracked < 1 || max_tracked > size_t(LCX_TRK_MAX))
+      throw lcx_error("libcloudph++: track: max_tracked = " + std::to_string(max_tracked) + " is outside 1 .. " + std::to_string(int(LCX_TRK_MAX)));
+    if (capacity < 1) throw lcx_error("libcloudph++: track: capacity == 0");
+    if (every < 0) throw lcx_error("libcloudph++: track: every = " + std::to_string(every) + " < 0");
+    if (ix_trk < 0 && n_ext >= MAX_EXT) throw lcx_error("libcloudph++: track: no free attribute column (all " + std::to_string(MAX_EXT) + " are in use)");
+    HIPCHK(hipStreamSynchronize(st));              // (a kernel still queued may read what a new size re-allocates)
+    if (ix_trk < 0) {
+      A.ext[n_ext].alloc(cap);
+      if (B.n.p) B.ext[n_ext].alloc(cap);          // (else alloc_attrs(B) makes it with the others)
+      ix_trk = n_ext++;
+    }
+    HIPCHK(hipMemsetAsync(A.ext[ix_trk].p, 0, cap * sizeof(T), st));
+    if (trk_slot_of.n != max_tracked) { trk_slot_of.release(); trk_slot_of.alloc(max_tracked); }
+    const size_t elems = track::buf_elems(capacity, max_tracked);
+    if (trk_buf.n != elems) { trk_buf.release(); trk_buf.alloc(elems); }
+    trk_max = max_tracked; trk_cap = capacity; trk_every = every;
+    trk_steps.assign(capacity, 0ull); trk_times.assign(capacity, 0.);
+    trk_n = 0; trk_ns = 0; trk_dropped = 0; trk_scans = 0; trk_step_count = 0; trk_time_now = 0;
+    trk_stale = true;
+  }
+  void track_disable() override
+  {
+    trk_need("disable");
+    HIPCHK(hipStreamSynchronize(st));
+    --n_ext;                                       // (ix_trk == n_ext - 1: the last column)
+    A.ext[ix_trk].release(); B.ext[ix_trk].release();
+    ix_trk = -1; trk_every = 0; trk_stale = false;
+    trk_max = trk_n = trk_cap = trk_ns = 0; trk_dropped = trk_scans = trk_step_count = 0; trk_time_now = 0;
+    trk_slot_of.release(); trk_part.release(); trk_total.release(); trk_ids.release(); trk_buf.release(); trk_out.release(); trk_slots_in.release(); trk_ok.release();
+    trk_steps = {}; trk_times = {}; trk_host = {};
+  }
+  void track_info(int *enabled, size_t *max_tracked, size_t *n_tracked, size_t *capacity, size_t *n_samples, unsigned long long *dropped, int *every,
+                  unsigned long long *scans) override
+  {
+    if (enabled) *enabled = ix_trk >= 0 ? 1 : 0;
+    if (max_tracked) *max_tracked = trk_max;
+    if (n_tracked) *n_tracked = trk_n;
+    if (capacity) *capacity = trk_cap;
+    if (n_samples) *n_samples = trk_ns;
+    if (dropped) *dropped = trk_dropped;
+    if (every) *every = trk_every;
+    if (scans) *scans = trk_scans;
+  }
+  void trk_need(const char *what) const { if (ix_trk < 0) throw lcx_error(std::string("libcloudph++: track: ") + what + " while tracking is not enabled (lcx_track_enable)"); }
+  void trk_need_init(const char *what) const { if (!init_called) throw lcx_error(std::string("libcloudph++: track: ") + what + " before init()"); }
+  // slot_of from the mark column, where storage has been permuted since it was last made
+  void trk_refresh_slots()
+  {
+    if (!trk_stale || !trk_n) return;              // (nothing is marked yet: the list stays stale, as enable left it, until a sample needs it)
+    trk_stale = false;
+    HIPCHK(hipMemsetAsync(trk_slot_of.p, 0xFF, trk_max * sizeof(uint32_t), st));      // (= track::NONE)
+    if (nphys) hipLaunchKernelGGL(k_track_scan<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, (const T *)A.ext[ix_trk].p, trk_slot_of.p, uint32_t(trk_max));
+    ++trk_scans;
+  }
+  // one sample on the stream, no host wait
+  void trk_take_sample()
+  {
+    if (trk_ns >= trk_cap) { ++trk_dropped; return; }
+    Range r(this, "track_sample");
+    const size_t s = trk_ns++;
+    trk_steps[s] = trk_step_count; trk_times[s] = trk_time_now;
+    if (!trk_n) return;
+    trk_refresh_slots();
+    track_sample_arg<T> a{trk_slot_of.p, A.n.p, A.ext[ix_trk].p, A.x.p, A.y.p, A.z.p, A.rw2.p, A.rd3.p, A.kpa.p, A.vt.p, ijk.p, Tk.p, RH.p, rv.p, nphys, ncell};
+    hipLaunchKernelGGL(k_track_sample<T>, dim3(nblk(trk_n)), dim3(BS), 0, st, uint32_t(trk_n), a, trk_buf.p + track::buf_offset(s, 0, 0, trk_max), trk_max);
+  }
+  void trk_after_step()
+  {
+    ++trk_step_count; trk_time_now += dt;
+    if (trk_every > 0 && trk_step_count % (unsigned long long)trk_every == 0) trk_take_sample();
+  }
+  void track_sample() override { trk_need("sample"); trk_need_init("sample"); trk_take_sample(); }
+  // the indices [n0, trk_n) are new: absent in every sample held
+  void trk_grown(size_t n0)
+  {
+    if (trk_n == n0 || !trk_ns) return;
+    const size_t m = trk_ns * size_t(LCX_TRK_FIELDS) * (trk_n - n0);
+    hipLaunchKernelGGL(k_track_absent, dim3(nblk(m)), dim3(BS), 0, st, trk_buf.p, trk_ns, n0, trk_n, trk_max);
+  }
+  void track_select(const lcx_diag_clause_t *clause, int n_clauses, const double *box, size_t max_count, size_t *n_selected) override
+  {
+    trk_need("select"); trk_need_init("select");
+    const bool pair[3] = {o.nx != 0, o.ny != 0, o.nz != 0};
+    std::string err;
+    if (!track::validate(clause, n_clauses, box, max_count, err, pair)) throw lcx_error(err);
+    if (n_selected) *n_selected = 0;
+    const size_t room = size_t(track::room(max_count, trk_max, trk_n));
+    if (!room || !nphys) { sync(); return; }
+    trk_refresh_slots();                           // (the slots of the earlier indices, while the marks still say them)
+    track_sel_arg<T> a{A.n.p, A.ext[ix_trk].p, A.rd3.p, A.rw2.p, A.kpa.p, A.x.p, A.y.p, A.z.p, n_clauses, {}, {}, {}, box ? 1 : 0, {0, 0, 0, 0, 0, 0}};
+    for (int c = 0; c < n_clauses; ++c) {
+      double lo = 0, hi = 0;
+      a.sel[c] = clause[c].sel;
+      if (diag::sel_is_range(clause[c].sel)) diag::rng_bounds(clause[c].sel, clause[c].lo, clause[c].hi, lo, hi);
+      a.lo[c] = T(lo); a.hi[c] = T(hi);
+    }
+    if (box) for (int d = 0; d < 3; ++d) if (pair[d]) { a.box[2 * d] = box[2 * d]; a.box[2 * d + 1] = box[2 * d + 1]; }
+    const size_t tiles = (nphys + SCAN_TILE - 1) / SCAN_TILE;
+    trk_part.alloc(tiles); trk_total.alloc(1);
+    hipLaunchKernelGGL(k_track_count<T>, dim3(unsigned(tiles)), dim3(BS), 0, st, nphys, a, trk_part.p);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, trk_part.p, tiles, trk_total.p);
+    uint32_t Q = 0;
+    read_back(&Q, trk_total.p, 1);
+    const uint64_t stride = track::stride(Q, room);
+    if (!stride) return;
+    const size_t took = size_t(track::count(Q, stride)), n0 = trk_n;
+    hipLaunchKernelGGL(k_track_assign<T>, dim3(unsigned(tiles)), dim3(BS), 0, st, nphys, a, (const uint32_t *)trk_part.p, stride, uint32_t(trk_n), uint32_t(trk_max), trk_slot_of.p);
+    trk_n += took;
+    trk_grown(n0);
+    sync();
+    if (n_selected) *n_selected = took;
+  }
+  void track_select_slots(const unsigned long long *slot, size_t n, size_t *n_selected) override
+  {
+    trk_need("select_slots"); trk_need_init("select_slots");
+    if (n && !slot) throw lcx_error("libcloudph++: track: slot == NULL with n > 0");
+    if (n_selected) *n_selected = 0;
+    if (!n || trk_n >= trk_max) return;
+    trk_refresh_slots();
+    trk_slots_in.alloc(n); trk_ok.alloc(n);
+    HIPCHK(hipMemcpyAsync(trk_slots_in.p, slot, n * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_track_slots_probe<T>, dim3(nblk(n)), dim3(BS), 0, st, n, (const unsigned long long *)trk_slots_in.p, nphys, (const n_t *)A.n.p,
+                       (const T *)A.ext[ix_trk].p, trk_ok.p);
+    std::vector<uint8_t> ok = d2h(trk_ok.p, n);
+    std::vector<uint32_t> take; std::unordered_set<unsigned long long> seen;
+    for (size_t t = 0; t < n && trk_n + take.size() < trk_max; ++t) {
+      if (!ok[t] || !seen.insert(slot[t]).second) continue;          // (a slot given twice is taken once, at its first place)
+      take.push_back(uint32_t(slot[t]));
+    }
+    if (take.empty()) return;
+    const size_t n0 = trk_n;
+    trk_ids.alloc(take.size());
+    HIPCHK(hipMemcpyAsync(trk_ids.p, take.data(), take.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_track_slots_apply<T>, dim3(nblk(take.size())), dim3(BS), 0, st, take.size(), (const uint32_t *)trk_ids.p, uint32_t(trk_n), A.ext[ix_trk].p, trk_slot_of.p);
+    trk_n += take.size();
+    trk_grown(n0);
+    sync();                                        // (`take` is read by the copy until here)
+    if (n_selected) *n_selected = take.size();
+  }
+  void track_read(double *out, size_t sample_stride, size_t field_stride, unsigned long long *steps, double *time, size_t cap_samples, size_t *n_samples,
+                  bool on_device, bool reset) override
+  {
+    trk_need("read");
+    if (field_stride < trk_n) throw lcx_error("libcloudph++: track: field_stride (" + std::to_string(field_stride) + ") < n_tracked (" + std::to_string(trk_n) + ")");
+    if (sample_stride < size_t(LCX_TRK_FIELDS) * field_stride)
+      throw lcx_error("libcloudph++: track: sample_stride (" + std::to_string(sample_stride) + ") < " + std::to_string(int(LCX_TRK_FIELDS)) + " * field_stride (" + std::to_string(field_stride) + ")");
+    if (cap_samples < trk_ns) throw lcx_error("libcloudph++: track: cap_samples (" + std::to_string(cap_samples) + ") < the samples held (" + std::to_string(trk_ns) + ")");
+    const size_t m = trk_ns * size_t(LCX_TRK_FIELDS) * trk_n;
+    if (m && !out) throw lcx_error("libcloudph++: track: out == NULL with samples to write");
+    if (m) {
+      if (on_device) hipLaunchKernelGGL(k_track_read, dim3(nblk(m)), dim3(BS), 0, st, (const double *)trk_buf.p, trk_ns, trk_n, trk_max, out, sample_stride, field_stride);
+      else {
+        trk_out.alloc(m); trk_host.resize(m);
+        hipLaunchKernelGGL(k_track_read, dim3(nblk(m)), dim3(BS), 0, st, (const double *)trk_buf.p, trk_ns, trk_n, trk_max, trk_out.p, size_t(LCX_TRK_FIELDS) * trk_n, trk_n);
+        HIPCHK(hipMemcpyAsync(trk_host.data(), trk_out.p, m * sizeof(double), hipMemcpyDeviceToHost, st));
+      }
+    }
+    sync();
+    if (m && !on_device)
+      for (size_t s = 0; s < trk_ns; ++s) for (int f = 0; f < LCX_TRK_FIELDS; ++f)
+        memcpy(out + s * sample_stride + size_t(f) * field_stride, trk_host.data() + (s * size_t(LCX_TRK_FIELDS) + size_t(f)) * trk_n, trk_n * sizeof(double));
+    for (size_t s = 0; s < trk_ns; ++s) { if (steps) steps[s] = trk_steps[s]; if (time) time[s] = trk_times[s]; }
+    if (n_samples) *n_samples = trk_ns;
+    if (reset) { trk_ns = 0; trk_dropped = 0; }
+  }
   void refresh_n_max()
   {
     if (!n_max_stale) return;
@@ -2499,6 +2692,7 @@ struct Particles : IParticles {
     for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0) HIPCHK(hipMemsetAsync(A.ext[ix].p + n_old, 0, n_new * sizeof(T), st));
     if (ix_rc2 >= 0) hipLaunchKernelGGL(k_fill<T>, dim3(nblk(n_new)), dim3(BS), 0, st, A.ext[ix_rc2].p + n_old, n_new, T(-1));
     if (ix_tag >= 0) hipLaunchKernelGGL(k_fill_index_from<T>, dim3(nblk(n_new)), dim3(BS), 0, st, A.ext[ix_tag].p + n_old, n_new, T(tag_next));
+    if (ix_trk >= 0) HIPCHK(hipMemsetAsync(A.ext[ix_trk].p + n_old, 0, n_new * sizeof(T), st));     // (include/lcx_track.h: a newcomer has mark 0)
     tag_next += n_new;
     nphys = n_old + n_new;
     zero_n_unmarked = true;                          // (a multiplicity may round to zero; matching clears those it hands on)
@@ -3072,6 +3266,7 @@ struct Particles : IParticles {
     n_before_unpack = nphys;
     if (fused && !distmem()) post_copy_after_fused_move(opts);
     else if (!distmem()) post_copy(opts);
+    if (ix_trk >= 0) trk_after_step();               // (include/lcx_track.h: the step counts, and every every-th one ends in a sample)
     // no host synchronisation here: step_async hands no array back, everything later is ordered on the object's stream and
     // every call that returns data to the host synchronises itself -- the caller's next step_sync is queued while this one runs
     selected_before_counting = false;
@@ -3335,6 +3530,7 @@ struct Particles : IParticles {
     struct E { const char *nm; const T *p; size_t len; };
     const E tab[] = {{"raw_rw2", A.rw2.p, nphys}, {"raw_rd3", A.rd3.p, nphys}, {"raw_kappa", A.kpa.p, nphys}, {"raw_vt", A.vt.p, nphys},
       {"raw_x", A.x.p, A.x.p ? nphys : 0}, {"raw_y", A.y.p, A.y.p ? nphys : 0}, {"raw_z", A.z.p, A.z.p ? nphys : 0},
+      {"raw_track", ix_trk >= 0 ? A.ext[ix_trk].p : nullptr, ix_trk >= 0 ? nphys : 0},       // (include/lcx_track.h: k + 1 per storage slot, 0 unmarked)
       {"raw_tag", ix_tag >= 0 ? A.ext[ix_tag].p : nullptr, ix_tag >= 0 ? nphys : 0}, {"tag", ix_tag >= 0 ? A.ext[ix_tag].p : nullptr, ix_tag >= 0 ? npart : 0},
       {"vt", A.vt.p, npart}, {"T", Tk.p, ncell}, {"p", p.p, ncell}, {"RH", RH.p, ncell}, {"eta", eta.p, ncell}, {"th", th.p, ncell},
       {"rv", rv.p, ncell}, {"rhod", rhod.p, ncell}, {"dv", dv.p, ncell}, {"lambda_D", lambda_D.p, ncell}, {"lambda_K", lambda_K.p, ncell},
@@ -3392,6 +3588,7 @@ struct Particles : IParticles {
     for (int ix : {ix_up, ix_vp, ix_wp, ix_ssp, ix_dot_ssp, ix_ict}) if (ix >= 0 && n) HIPCHK(hipMemsetAsync(A.ext[ix].p, 0, n * sizeof(T), st));
     if (ix_tag >= 0 && n) hipLaunchKernelGGL(k_fill_index<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_tag].p, n);
     tag_next = n;
+    if (ix_trk >= 0) { if (n) HIPCHK(hipMemsetAsync(A.ext[ix_trk].p, 0, n * sizeof(T), st)); trk_stale = true; }     // (include/lcx_track.h)
     if (o.chem_switch) chem_init_masses(n);
     if (use_rc2 && n) { hipLaunchKernelGGL(k_fill<T>, dim3(nblk(n)), dim3(BS), 0, st, A.ext[ix_rc2].p, n, T(-1)); hskpng_approximate_rc2_invalid(); }
     sstp_save();
@@ -3789,6 +3986,7 @@ struct Particles : IParticles {
     if (o.nz) f("z", A.z, n, snap::ELEM_REAL);
     static const char *const chem_names[CH_ALL] = {"HNO3", "NH3", "CO2", "SO2", "H2O2", "O3", "S_VI", "H"};
     for (int e = 0; e < n_ext; ++e) {
+      if (e == ix_trk) continue;                     // (include/lcx_track.h: the mark is not part of a snapshot)
       std::string nm = "ext" + std::to_string(e);
       if (e == ix_rv) nm = "sstp_tmp_rv"; else if (e == ix_th) nm = "sstp_tmp_th"; else if (e == ix_rh) nm = "sstp_tmp_rh"; else if (e == ix_p) nm = "sstp_tmp_p";
       else if (e == ix_rc2) nm = "rc2"; else if (e == ix_up) nm = "up"; else if (e == ix_vp) nm = "vp"; else if (e == ix_wp) nm = "wp"; else if (e == ix_ssp) nm = "ssp";
@@ -3932,6 +4130,39 @@ struct Particles : IParticles {
     hipLaunchKernelGGL(k_checksum64, dim3(blocks), dim3(CKS_BS), 0, st, (const unsigned char *)dev, bytes, snap_cks.p);
     hipLaunchKernelGGL(k_checksum64_fold, dim3(1), dim3(CKS_BS), 0, st, (const uint64_t *)snap_cks.p, blocks, snap_cks.p + CKS_MAX_BLOCKS + slot);
   }
+  // Two sections keep what atomics left, in an order that differs from run to run: `big_list` (crowded cells as k_list_big_cells appended
+  // them, and behind them the tail of older lists) and `rank` (arrival ranks; once scattered, the ranking's scratch).  Their COPIES are
+  // written in one form, so that equal runs give equal bytes; the object's own arrays are not touched, and everything happens on the
+  // device, in scratch that is written before it is read anyway (m3_before / m3_after: 4 B per slot at least) and one list of ncell + 1.
+  // big_list: the cells above big_thr ascending and 0 behind them (the very set that was listed -- cell_start has not changed since; every
+  // listed cell is sorted by itself, sort_listed_cells), all 0 where the list is stale (order_cells lists anew).  rank: with the scatter
+  // still owed (sort_deferred) a cell's ranks in storage order -- any bijection onto the cell's segment serves k_scatter_sorted and the
+  // ranking behind it -- else 0 (every later user of `rank` writes it first).  A list whose count is still on the device goes as it is.
+  DevBuf<uint32_t> snap_list, snap_ids, snap_rank;
+  const uint32_t *snap_canonical_list()
+  {
+    if (listed_from_hist || meta_known_valid) return big_list.p;
+    snap_list.alloc(ncell + 1);
+    if (meta_version == cells_version)
+      hipLaunchKernelGGL(k_snap_list_big, dim3(1), dim3(1024), 0, st, ncell, (const uint32_t *)cell_start.p, big_thr, snap_list.p, ncell + 1);
+    else HIPCHK(hipMemsetAsync(snap_list.p, 0, (ncell + 1) * sizeof(uint32_t), st));
+    return snap_list.p;
+  }
+  const uint32_t *snap_canonical_rank()
+  {
+    const size_t bytes = nphys * sizeof(uint32_t);
+    const bool lend = m3_before.n * sizeof(T) >= bytes && m3_after.n * sizeof(T) >= bytes;
+    if (!lend) { snap_ids.alloc(nphys); snap_rank.alloc(nphys); }
+    uint32_t *ids = lend ? reinterpret_cast<uint32_t *>(m3_before.p) : snap_ids.p, *out = lend ? reinterpret_cast<uint32_t *>(m3_after.p) : snap_rank.p;
+    HIPCHK(hipMemsetAsync(out, 0, bytes, st));
+    if (sort_deferred) {
+      const size_t live = std::min(npart, nphys);
+      HIPCHK(hipMemsetAsync(ids, 0xFF, bytes, st));
+      hipLaunchKernelGGL(k_snap_scatter_ids, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, ncell, (const uint32_t *)ijk.p, (const uint32_t *)rnk(), (const uint32_t *)cell_start.p, ids);
+      if (live) hipLaunchKernelGGL(k_snap_rank_ids, dim3(nblk(live)), dim3(BS), 0, st, live, nphys, ncell, (const uint32_t *)ijk.p, (const uint32_t *)cell_start.p, (const uint32_t *)ids, out);
+    }
+    return out;
+  }
   size_t snapshot_size() override { snap_refuse_unless_quiet(); return size_t(snap_layout().total_bytes); }
   size_t snapshot_save(void *buf, size_t capb) override
   {
@@ -3944,12 +4175,15 @@ struct Particles : IParticles {
     {
       SnapStager sg(st, size_t(snap::CHUNK_BYTES));
       size_t slot = 0;
-      snap_arrays([&](const char *, auto &dbuf, size_t count, uint32_t) {
+      snap_arrays([&](const char *nm, auto &dbuf, size_t count, uint32_t) {
         if (!dbuf.p || !count) return;
         const snap::section &s = L.sections[slot];
         const size_t bytes = count * sizeof(*dbuf.p);
-        snap_checksum_async(dbuf.p, bytes, slot);        // while the data is in HBM, ahead of its copy on the same stream
-        sg.d2h(b + s.offset, dbuf.p, bytes);
+        const void *src = dbuf.p;
+        if (!strcmp(nm, "rank")) src = snap_canonical_rank();
+        else if (!strcmp(nm, "big_list")) src = snap_canonical_list();
+        snap_checksum_async(src, bytes, slot);           // while the data is in HBM, ahead of its copy on the same stream
+        sg.d2h(b + s.offset, src, bytes);
         memset(b + s.offset + bytes, 0, size_t(snap::align_up(s.offset + bytes) - (s.offset + bytes)));
         ++slot;
       });
@@ -4072,6 +4306,7 @@ struct Particles : IParticles {
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)
       move_rates_disable();                        // (include/lcx_move_rates.h: the same)
+      if (ix_trk >= 0) track_disable();            // (include/lcx_track.h: the same)
     } catch (...) { roll_back(); throw; }
   }
   // what the constructor left zero and a load that failed half-way may have written
@@ -4358,6 +4593,26 @@ int lcx_move_rates_info(lcx_particles *h, int *enabled, int *n_thr, double *r_th
 int lcx_move_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
 { LCX_TRY(H->move_rates_read(out, stride, out_on_device != 0, reset != 0)) }
 int lcx_diag_move_rate(lcx_particles *h, int row) { LCX_TRY(H->diag_move_rate(row)) }
+// ---- tracked super-droplets (include/lcx_track.h) ----
+int lcx_track_check(const lcx_diag_clause_t *clause, int n_clauses, const double *box, size_t max_count)
+{
+  std::string err;                                   // (host only: no device is looked for or bound)
+  if (lcx::track::validate(clause, n_clauses, box, max_count, err)) return 0;
+  g_err = err;
+  return 1;
+}
+int lcx_track_enable(lcx_particles *h, size_t max_tracked, size_t capacity, int every) { LCX_TRY(H->track_enable(max_tracked, capacity, every)) }
+int lcx_track_disable(lcx_particles *h) { LCX_TRY(H->track_disable()) }
+int lcx_track_select(lcx_particles *h, const lcx_diag_clause_t *clause, int n_clauses, const double *box, size_t max_count, size_t *n_selected)
+{ LCX_TRY(H->track_select(clause, n_clauses, box, max_count, n_selected)) }
+int lcx_track_select_slots(lcx_particles *h, const unsigned long long *slot, size_t n, size_t *n_selected) { LCX_TRY(H->track_select_slots(slot, n, n_selected)) }
+int lcx_track_sample(lcx_particles *h) { LCX_TRY(H->track_sample()) }
+int lcx_track_info(lcx_particles *h, int *enabled, size_t *max_tracked, size_t *n_tracked, size_t *capacity, size_t *n_samples, unsigned long long *dropped,
+                   int *every, unsigned long long *scans)
+{ LCX_TRY(H->track_info(enabled, max_tracked, n_tracked, capacity, n_samples, dropped, every, scans)) }
+int lcx_track_read(lcx_particles *h, double *out, size_t sample_stride, size_t field_stride, unsigned long long *steps, double *time, size_t cap_samples,
+                   size_t *n_samples, int out_on_device, int reset)
+{ LCX_TRY(H->track_read(out, sample_stride, field_stride, steps, time, cap_samples, n_samples, out_on_device != 0, reset != 0)) }
 // ---- condensation rates per cell (include/lcx_cond_rates.h) ----
 int lcx_cond_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->cond_rates_enable(r_thr, n_thr)) }
 int lcx_cond_rates_disable(lcx_particles *h) { LCX_TRY(H->cond_rates_disable()) }

@@ -14,6 +14,7 @@
 #include "lcx_cond_wq.hpp"
 #include "lcx_diag_plan.hpp"
 #include "lcx_coal_prevote.hpp"
+#include "lcx_track_plan.hpp"
 
 namespace lcx {
 
@@ -650,6 +651,54 @@ __global__ void k_list_big_cells(size_t n_cell, const uint32_t *cell_start, uint
   if (lane_id() == 0) { base = atomicAdd(big_count, uint32_t(__popcll(bal))); atomicMax(big_max, mx); }
   base = __shfl(base, 0);
   if (big) big_list[base + __popcll(bal & ((1ull << lane_id()) - 1ull))] = uint32_t(c);
+}
+// ---- a snapshot's copies of `big_list` and `rank` in a form that does not depend on the order in which atomics arrived (lcx_core.hip) ----
+// the cells with more than `thr` SDs ASCENDING, 0 behind them up to n_out: ONE workgroup walks the cells 1024 at a time and carries the
+// offset (a snapshot's pace is the copy of every attribute to the host; 2^21 cells are 2048 rounds)
+__global__ void __launch_bounds__(1024) k_snap_list_big(size_t n_cell, const uint32_t *cell_start, uint32_t thr, uint32_t *out, size_t n_out)
+{
+  __shared__ uint32_t wsum[1024 / WAVE];
+  uint32_t base = 0;
+  for (size_t c0 = 0; c0 < n_cell; c0 += 1024) {
+    const size_t c = c0 + threadIdx.x;
+    const bool big = c < n_cell && cell_start[c + 1] - cell_start[c] > thr;
+    const unsigned long long bal = __ballot(big);
+    if (lane_id() == 0) wsum[wave_id()] = uint32_t(__popcll(bal));
+    __syncthreads();
+    uint32_t off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 1024 / WAVE; ++w) { const uint32_t v = wsum[w]; if (w < int(wave_id())) off += v; tot += v; }
+    const size_t q = size_t(base) + off + uint32_t(__popcll(bal & ((1ull << lane_id()) - 1ull)));
+    if (big && q < n_out) out[q] = uint32_t(c);
+    base += tot;
+    __syncthreads();
+  }
+  for (size_t q = size_t(base) + threadIdx.x; q < n_out; q += 1024) out[q] = 0u;
+}
+// the scatter that is owed, into scratch: ids[cell_start[c] + rank[i]] = i (ids preset to ~0: a hole stays recognisable)
+__global__ void k_snap_scatter_ids(size_t n, size_t n_cell, const uint32_t *ijk, const uint32_t *rank, const uint32_t *cell_start, uint32_t *ids)
+{
+  const size_t i = gid();
+  if (i >= n) return;
+  const uint32_t c = ijk[i];
+  if (c == DEAD_CELL || c >= n_cell) return;
+  const size_t pos = size_t(cell_start[c]) + rank[i];
+  if (pos < n) ids[pos] = uint32_t(i);
+}
+// a lane per scattered id: its rank is the number of smaller ids in its cell's segment, i.e. the cell's droplets in storage order
+// (out preset to 0: dead slots keep 0)
+__global__ void k_snap_rank_ids(size_t n_live, size_t n, size_t n_cell, const uint32_t *ijk, const uint32_t *cell_start, const uint32_t *ids, uint32_t *out)
+{
+  const size_t p = gid();
+  if (p >= n_live) return;
+  const uint32_t id = ids[p];
+  if (id >= n) return;
+  const uint32_t c = ijk[id];
+  if (c == DEAD_CELL || c >= n_cell) return;
+  const size_t s = cell_start[c], e = cell_start[c + 1] < n ? cell_start[c + 1] : n;
+  uint32_t r = 0;
+  for (size_t q = s; q < e; ++q) r += ids[q] < id;
+  out[id] = r;
 }
 // listed segments of up to CELLSORT_WAVE_MAX keys (e.g. 512 SDs per cell): ONE WAVE per segment, bitonic network on a
 // power-of-two padded copy in a wave-private LDS slice.  No workgroup barriers: a wave executes its LDS instructions in
@@ -4814,5 +4863,149 @@ __global__ void __launch_bounds__(BS) k_chem_puddle_sum(const double *partial, s
   }
   if (threadIdx.x < CH_ALL) running[threadIdx.x] = running[threadIdx.x] + red[threadIdx.x][0];
 }
+
+// ============================================================================================
+// tracked super-droplets (include/lcx_track.h; the integer rules: lcx_track_plan.hpp)
+// ============================================================================================
+// The mark column holds k + 1 for track index k and 0 otherwise.  slot_of[k] is the storage slot that carries mark k + 1, or NONE.
+// k_track_scan: a lane per storage slot reads the mark alone; the target of a non-zero mark is known, so no atomic and no compaction.
+// slot_of has been set to NONE ahead of it (a memset of 0xFF).
+template <class T>
+__global__ void k_track_scan(size_t n_storage, const T *mark, uint32_t *slot_of, uint32_t max_tracked)
+{
+  const size_t i = gid(); if (i >= n_storage) return;
+  const T m = mark[i];
+  if (m == T(0)) return;
+  const uint32_t k = uint32_t(m) - 1u;
+  if (k < max_tracked) slot_of[k] = uint32_t(i);
+}
+// A lane per track index: the slot, the eight attributes, the cell and the cell's T, RH and rv, written field-major (a wave's stores to one
+// field are contiguous in k).  The absent pattern where there is no slot, the slot no longer carries the mark, or n == 0.
+template <class T> struct track_sample_arg {
+  const uint32_t *slot_of; const n_t *n; const T *mark, *x, *y, *z, *rw2, *rd3, *kpa, *vt; const uint32_t *ijk; const T *Tk, *RH, *rv;
+  size_t n_storage, n_cell;
+};
+template <class T>
+__global__ void k_track_sample(uint32_t n_tracked, track_sample_arg<T> a, double *dst /* the sample's 12 rows */, size_t max_tracked)
+{
+  const size_t k = gid(); if (k >= n_tracked) return;
+  const uint32_t s = a.slot_of[k];
+  n_t nn = 0;
+  if (s != track::NONE && s < a.n_storage && a.mark[s] == T(k + 1)) nn = a.n[s];
+  const double nan = __builtin_nan("");
+  double v[LCX_TRK_FIELDS];
+#pragma unroll
+  for (int f = 0; f < LCX_TRK_FIELDS; ++f) v[f] = nan;
+  v[LCX_TRK_N] = double(nn);
+  if (nn) {
+    v[LCX_TRK_X] = a.x ? double(a.x[s]) : 0.; v[LCX_TRK_Y] = a.y ? double(a.y[s]) : 0.; v[LCX_TRK_Z] = a.z ? double(a.z[s]) : 0.;
+    v[LCX_TRK_RW2] = double(a.rw2[s]); v[LCX_TRK_RD3] = double(a.rd3[s]); v[LCX_TRK_KAPPA] = double(a.kpa[s]); v[LCX_TRK_VT] = double(a.vt[s]);
+    const uint32_t c = a.ijk[s];
+    v[LCX_TRK_CELL] = double(c);
+    if (c < a.n_cell) { v[LCX_TRK_T] = double(a.Tk[c]); v[LCX_TRK_RH] = double(a.RH[c]); v[LCX_TRK_RV] = double(a.rv[c]); }
+  }
+#pragma unroll
+  for (int f = 0; f < LCX_TRK_FIELDS; ++f) dst[track::buf_offset(0, f, k, max_tracked)] = v[f];
+}
+// the absent pattern for the indices [k0, k1) in the samples [0, n_samples): what a selection leaves in the samples taken before it
+__global__ void k_track_absent(double *buf, size_t n_samples, size_t k0, size_t k1, size_t max_tracked)
+{
+  const size_t w = k1 - k0, per = size_t(LCX_TRK_FIELDS) * w;
+  const size_t i = gid(); if (i >= n_samples * per) return;
+  const size_t s = i / per, f = (i - s * per) / w, k = k0 + (i - s * per) % w;
+  buf[track::buf_offset(s, int(f), k, max_tracked)] = f == LCX_TRK_N ? 0. : __builtin_nan("");
+}
+// out[s * sample_stride + f * field_stride + k] for k < n_tracked: lcx_track_read
+__global__ void k_track_read(const double *buf, size_t n_samples, size_t n_tracked, size_t max_tracked, double *out, size_t sample_stride, size_t field_stride)
+{
+  const size_t per = size_t(LCX_TRK_FIELDS) * n_tracked;
+  const size_t i = gid(); if (i >= n_samples * per) return;
+  const size_t s = i / per, f = (i - s * per) / n_tracked, k = (i - s * per) % n_tracked;
+  out[s * sample_stride + f * field_stride + k] = buf[track::buf_offset(s, int(f), k, max_tracked)];
+}
+
+// ---- selection: the predicate is ONE function for the count pass and the assign pass; the bounds come from the host, rounded there ----
+template <class T> struct track_sel_arg {
+  const n_t *n; T *mark; const T *rd3, *rw2, *kpa, *x, *y, *z;      // x, y, z: nullptr for a dimension the object lacks
+  int n_clauses, sel[LCX_DIAG_MAX_CLAUSES]; T lo[LCX_DIAG_MAX_CLAUSES], hi[LCX_DIAG_MAX_CLAUSES];
+  int has_box; double box[6];
+};
+template <class T> __device__ __forceinline__ bool track_qualifies(const track_sel_arg<T> &a, size_t i)
+{
+  if (a.n[i] == 0 || a.mark[i] != T(0)) return false;
+  T y = T(1);
+  for (int cl = 0; cl < a.n_clauses; ++cl) {
+    const int sel = a.sel[cl];
+    if (sel == LCX_DIAG_SEL_ALL) continue;
+    const T v = sel == LCX_DIAG_SEL_DRY ? a.rd3[i] : sel == LCX_DIAG_SEL_KAPPA ? a.kpa[i] : a.rw2[i];
+    y = nfilt_step(sel == LCX_DIAG_SEL_WATER ? 2 : 1, y, v, a.lo[cl], a.hi[cl]);
+  }
+  if (!(y > T(0))) return false;
+  if (a.has_box) {
+    if (a.x) { const double p = double(a.x[i]); if (!(p >= a.box[0] && p < a.box[1])) return false; }
+    if (a.y) { const double p = double(a.y[i]); if (!(p >= a.box[2] && p < a.box[3])) return false; }
+    if (a.z) { const double p = double(a.z[i]); if (!(p >= a.box[4] && p < a.box[5])) return false; }
+  }
+  return true;
+}
+// count pass: a ballot and a popcount per wave, one partial per workgroup (a tile of SCAN_TILE slots, as k_compact's)
+template <class T>
+__global__ void __launch_bounds__(BS) k_track_count(size_t n_storage, track_sel_arg<T> a, uint32_t *partial)
+{
+  __shared__ uint32_t lds[BS / WAVE];
+  const size_t base = size_t(blockIdx.x) * SCAN_TILE;
+  uint32_t cnt = 0;
+  for (int it = 0; it < SCAN_TILE / BS; ++it) {
+    const size_t i = base + size_t(it) * BS + threadIdx.x;
+    const bool q = i < n_storage && track_qualifies(a, i);
+    cnt += uint32_t(__popcll(__ballot(q)));
+  }
+  if (lane_id() == 0) lds[wave_id()] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) { uint32_t s = 0; for (int w = 0; w < BS / WAVE; ++w) s += lds[w]; partial[blockIdx.x] = s; }
+}
+// assign pass: the predicate again; rank = the workgroup's offset + the lower waves' counts + the popcount of the lower lanes; the ranks
+// that the stride rule takes get their mark and their slot
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_track_assign(size_t n_storage, track_sel_arg<T> a, const uint32_t *tile_offs, uint64_t stride, uint32_t n_tracked, uint32_t max_tracked, uint32_t *slot_of)
+{
+  __shared__ uint32_t lds[BS / WAVE];
+  const size_t base = size_t(blockIdx.x) * SCAN_TILE;
+  uint32_t run = tile_offs[blockIdx.x];
+  for (int it = 0; it < SCAN_TILE / BS; ++it) {
+    const size_t i = base + size_t(it) * BS + threadIdx.x;
+    const bool ok = i < n_storage && track_qualifies(a, i);
+    const unsigned long long bal = __ballot(ok);
+    const uint32_t in_wave = __popcll(bal & ((1ull << lane_id()) - 1ull));
+    if (lane_id() == 0) lds[wave_id()] = __popcll(bal);
+    __syncthreads();
+    uint32_t woff = 0, tot = 0;
+    for (unsigned w = 0; w < BS / WAVE; ++w) { const uint32_t s = lds[w]; if (w < wave_id()) woff += s; tot += s; }
+    __syncthreads();
+    const uint64_t q = uint64_t(run) + woff + in_wave;
+    if (ok && track::taken(q, stride)) {
+      const uint64_t k = track::index_of(q, stride, n_tracked);
+      if (k < max_tracked) { a.mark[i] = T(k + 1); slot_of[k] = uint32_t(i); }
+    }
+    run += tot;
+  }
+}
+// lcx_track_select_slots: which of the given slots could be taken (in range, alive, unmarked); the host settles order and duplicates
+template <class T>
+__global__ void k_track_slots_probe(size_t m, const unsigned long long *slot, size_t n_storage, const n_t *n, const T *mark, uint8_t *ok)
+{
+  const size_t t = gid(); if (t >= m) return;
+  const unsigned long long s = slot[t];
+  ok[t] = uint8_t(s < n_storage && n[s] != 0 && mark[s] == T(0));
+}
+template <class T>
+__global__ void k_track_slots_apply(size_t m, const uint32_t *slot, uint32_t first, T *mark, uint32_t *slot_of)
+{
+  const size_t t = gid(); if (t >= m) return;
+  mark[slot[t]] = T(first + uint32_t(t) + 1u); slot_of[first + t] = slot[t];
+}
+// the receivers of a recycling are new droplets: k_rcyc_apply has copied the donor's columns, the mark goes back to 0
+template <class T> __global__ void k_track_unmark(size_t m, const uint32_t *slot, T *mark) { const size_t t = gid(); if (t < m) mark[slot[t]] = T(0); }
 
 } // namespace lcx

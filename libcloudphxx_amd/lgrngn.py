@@ -474,6 +474,55 @@ def move_rates_out(out, n_thr, n_cell):
     return ptr, strides[0], isinstance(out, DeviceArray)
 
 
+# ---- tracked super-droplets (include/lcx_track.h)
+TRACK_FIELDS = ("n", "x", "y", "z", "rw2", "rd3", "kappa", "vt", "cell", "T", "RH", "rv")      # enum LCX_TRK_*, in its order
+TRACK_MAX = 1 << 20                                                  # LCX_TRK_MAX
+
+
+def track_clauses(clauses):
+    """clauses in diag_batch's notation -- ("all",), ("rng", "dry" | "wet" | "kappa", lo, hi), ("water",); a trailing cons flag as there
+    is accepted and not read: the clauses are ANDed -- as (array of lcx_diag_clause_t, n)"""
+    clauses = list(clauses)
+    if not 1 <= len(clauses) <= DIAG_MAX_CLAUSES:
+        raise ValueError("libcloudph++: track: n_clauses = %d is outside 1 .. %d" % (len(clauses), DIAG_MAX_CLAUSES))
+    arr = (_diag_clause_c * DIAG_MAX_CLAUSES)()
+    for i, s in enumerate(clauses):
+        s = tuple(s)
+        if s and s[0] == "all" and len(s) == 1:
+            arr[i].sel = _DIAG_SEL["all"]
+        elif s and s[0] == "water" and len(s) in (1, 2):
+            arr[i].sel = _DIAG_SEL["water"]
+        elif s and s[0] == "rng" and len(s) in (4, 5) and s[1] in _DIAG_MOM:
+            arr[i].sel, arr[i].lo, arr[i].hi = _DIAG_SEL[s[1]], float(s[2]), float(s[3])
+        else:
+            raise ValueError("libcloudph++: track: cannot express clause %d: %r" % (i, s))
+    return arr, len(clauses)
+
+
+def track_box(box):
+    """None, or the six bounds (x0, x1, y0, y1, z0, z1) as lcx_track_select takes them"""
+    if box is None:
+        return None
+    b = [float(v) for v in np.asarray(box, dtype=np.float64).ravel()]
+    if len(b) != 6:
+        raise ValueError("libcloudph++: track: box must hold six bounds (x0, x1, y0, y1, z0, z1), not %d" % len(b))
+    if not all(np.isfinite(v) for v in b):
+        raise ValueError("libcloudph++: track: box: every bound must be finite")
+    if any(b[2 * d] > b[2 * d + 1] for d in range(3)):
+        raise ValueError("libcloudph++: track: box: lo > hi")
+    return (C.c_double * 6)(*b)
+
+
+def track_check(clauses, box=None, max_count=1, lib=None):
+    """lcx_track_check on clauses in diag_batch's notation and a box of six numbers; needs no GPU.  Raises the library's text."""
+    lib = lib if lib is not None else _lib.load()
+    arr, n = track_clauses(clauses)
+    b = None if box is None else (C.c_double * 6)(*[float(v) for v in box])
+    if lib.lcx_track_check(arr, C.c_int(n), b, C.c_size_t(max_count)) != 0:
+        lib.lcx_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.lcx_last_error().decode())
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -1065,6 +1114,84 @@ class particles_t:
         """fills outbuf() with one row (a name of MOVE_RATES at threshold t, or a row number), normalised as a diag_*_mom result"""
         n_thr = max(len(self.move_rates_info()[1]), 1)
         self._chk(self._f("diag_move_rate")(self._h, C.c_int(move_rate_index(name_or_row, t, n_thr))))
+
+    # -- tracked super-droplets (include/lcx_track.h; no reference counterpart)
+    def track_enable(self, max_tracked, capacity=64, every=0):
+        """start (or start over) tracking: room for max_tracked droplets and `capacity` samples; every > 0: every every-th step_async ends in
+        a sample.  Before or after init()."""
+        max_tracked, capacity, every = int(max_tracked), int(capacity), int(every)
+        if not 1 <= max_tracked <= TRACK_MAX:
+            raise ValueError("libcloudph++: track: max_tracked = %d is outside 1 .. %d" % (max_tracked, TRACK_MAX))
+        if capacity < 1:
+            raise ValueError("libcloudph++: track: capacity must be at least 1")
+        if every < 0:
+            raise ValueError("libcloudph++: track: every = %d < 0" % every)
+        self._chk(self._f("track_enable")(self._h, C.c_size_t(max_tracked), C.c_size_t(capacity), C.c_int(every)))
+
+    def track_disable(self):
+        self._chk(self._f("track_disable")(self._h))
+
+    def track_select(self, clauses=(("all",),), box=None, max_count=None):
+        """mark droplets that satisfy every clause (see track_clauses) and lie in box (x0, x1, y0, y1, z0, z1), at most max_count of them
+        (None: all the room), spread evenly over the storage; returns how many were taken"""
+        arr, n = track_clauses(clauses)
+        b = track_box(box)
+        if max_count is None:
+            max_count = TRACK_MAX
+        max_count = int(max_count)
+        if max_count < 1:
+            raise ValueError("libcloudph++: track: max_count must be at least 1")
+        got = C.c_size_t()
+        self._chk(self._f("track_select")(self._h, arr, C.c_int(n), b, C.c_size_t(max_count), C.byref(got)))
+        return got.value
+
+    def track_select_slots(self, slots):
+        """mark the given storage slots (indices into the raw_ state) in their order; returns how many were taken"""
+        sl = np.asarray(slots).ravel()
+        if sl.size and (not np.issubdtype(sl.dtype, np.integer) or (sl < 0).any()):
+            raise ValueError("libcloudph++: track: slots must be non-negative integers")
+        sl = np.ascontiguousarray(sl, dtype=np.uint64)
+        got = C.c_size_t()
+        self._chk(self._f("track_select_slots")(self._h, sl.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.c_size_t(sl.size), C.byref(got)))
+        return got.value
+
+    def track_sample(self):
+        self._chk(self._f("track_sample")(self._h))
+
+    def track_info(self):
+        """dict: enabled, max_tracked, n_tracked, capacity, n_samples, dropped, every, scans"""
+        en, ev = C.c_int(), C.c_int()
+        mx, nt, cp, ns = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        dr, sc = C.c_ulonglong(), C.c_ulonglong()
+        self._chk(self._f("track_info")(self._h, C.byref(en), C.byref(mx), C.byref(nt), C.byref(cp), C.byref(ns), C.byref(dr), C.byref(ev), C.byref(sc)))
+        return {"enabled": en.value, "max_tracked": mx.value, "n_tracked": nt.value, "capacity": cp.value, "n_samples": ns.value,
+                "dropped": dr.value, "every": ev.value, "scans": sc.value}
+
+    def track(self, reset=False, out=None):
+        """the samples held: a dict with one (n_samples, n_tracked) float64 array per name of TRACK_FIELDS, plus "steps" (uint64) and "time".
+        With out= (a DeviceArray of the object's device, (n_samples, 12, n_tracked) doubles with unit stride along the droplets) the
+        records go there instead and the dict holds "steps" and "time" only.  reset: empty the buffer behind the read."""
+        info = self.track_info()
+        ns, nt, nf = info["n_samples"], info["n_tracked"], len(TRACK_FIELDS)
+        steps, time = np.zeros(max(ns, 1), dtype=np.uint64), np.zeros(max(ns, 1), dtype=np.float64)
+        if out is None:
+            arr = np.zeros((max(ns, 1), nf, max(nt, 1)), dtype=np.float64)
+            ptr, ss, fs, on_device = arr.ctypes.data, nf * max(nt, 1), max(nt, 1), False
+        else:
+            if not isinstance(out, DeviceArray) or len(out.shape) != 3 or tuple(out.shape) != (ns, nf, nt):
+                raise ValueError("libcloudph++: track: out must be a DeviceArray of shape (n_samples, %d, n_tracked) = (%d, %d, %d)" % (nf, ns, nf, nt))
+            if nt > 1 and out.strides[2] != 1:
+                raise ValueError("libcloudph++: track: out must have unit stride along the droplets")
+            ptr, ss, fs, on_device = out.ptr, out.strides[0], out.strides[1], True
+        got = C.c_size_t()
+        self._chk(self._f("track_read")(self._h, C.c_void_p(ptr), C.c_size_t(ss), C.c_size_t(fs), steps.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                        time.ctypes.data_as(C.POINTER(C.c_double)), C.c_size_t(steps.size), C.byref(got), C.c_int(int(on_device)),
+                                        C.c_int(int(bool(reset)))))
+        res = {"steps": steps[:ns].copy(), "time": time[:ns].copy()}
+        if out is None:
+            for f, nm in enumerate(TRACK_FIELDS):
+                res[nm] = arr[:ns, f, :nt].copy()
+        return res
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
