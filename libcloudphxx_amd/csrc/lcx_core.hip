@@ -140,36 +140,34 @@ struct IParticles {
   // many selections and moments in one pass (include/lcx_diag.h); the list has been validated
   virtual void diag_batch(const lcx_diag_req_t *, int, void *, size_t, bool) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
   virtual void diag_batch_info(int *, size_t *) { throw std::runtime_error("libcloudph++: diag_batch on a multi-device object is not built"); }
+  // what is built for a single-device object only refuses here
+  [[noreturn]] static void not_built(const char *tag) { throw std::runtime_error(std::string("libcloudph++: ") + tag + " on a multi-device object is not built"); }
   // collision rates per cell (include/lcx_coal_rates.h): built for a single-device object
-  [[noreturn]] static void no_coal_rates() { throw std::runtime_error("libcloudph++: coal_rates on a multi-device object is not built"); }
-  virtual void coal_rates_enable(double) { no_coal_rates(); }
-  virtual void coal_rates_disable() { no_coal_rates(); }
-  virtual void coal_rates_info(int *, double *, unsigned long long *) { no_coal_rates(); }
-  virtual void coal_rates_read(double *, size_t, bool, bool) { no_coal_rates(); }
-  virtual void diag_coal_rate(int) { no_coal_rates(); }
+  virtual void coal_rates_enable(double) { not_built("coal_rates"); }
+  virtual void coal_rates_disable() { not_built("coal_rates"); }
+  virtual void coal_rates_info(int *, double *, unsigned long long *) { not_built("coal_rates"); }
+  virtual void coal_rates_read(double *, size_t, bool, bool) { not_built("coal_rates"); }
+  virtual void diag_coal_rate(int) { not_built("coal_rates"); }
   // condensation rates per cell (include/lcx_cond_rates.h): built for a single-device object
-  [[noreturn]] static void no_cond_rates() { throw std::runtime_error("libcloudph++: cond_rates on a multi-device object is not built"); }
-  virtual void cond_rates_enable(const double *, int) { no_cond_rates(); }
-  virtual void cond_rates_disable() { no_cond_rates(); }
-  virtual void cond_rates_info(int *, int *, double *, unsigned long long *) { no_cond_rates(); }
-  virtual void cond_rates_read(double *, size_t, bool, bool) { no_cond_rates(); }
-  virtual void diag_cond_rate(int) { no_cond_rates(); }
+  virtual void cond_rates_enable(const double *, int) { not_built("cond_rates"); }
+  virtual void cond_rates_disable() { not_built("cond_rates"); }
+  virtual void cond_rates_info(int *, int *, double *, unsigned long long *) { not_built("cond_rates"); }
+  virtual void cond_rates_read(double *, size_t, bool, bool) { not_built("cond_rates"); }
+  virtual void diag_cond_rate(int) { not_built("cond_rates"); }
   // move rates per cell (include/lcx_move_rates.h): built for a single-device object
-  [[noreturn]] static void no_move_rates() { throw std::runtime_error("libcloudph++: move_rates on a multi-device object is not built"); }
-  virtual void move_rates_enable(const double *, int) { no_move_rates(); }
-  virtual void move_rates_disable() { no_move_rates(); }
-  virtual void move_rates_info(int *, int *, double *, unsigned long long *) { no_move_rates(); }
-  virtual void move_rates_read(double *, size_t, bool, bool) { no_move_rates(); }
-  virtual void diag_move_rate(int) { no_move_rates(); }
+  virtual void move_rates_enable(const double *, int) { not_built("move_rates"); }
+  virtual void move_rates_disable() { not_built("move_rates"); }
+  virtual void move_rates_info(int *, int *, double *, unsigned long long *) { not_built("move_rates"); }
+  virtual void move_rates_read(double *, size_t, bool, bool) { not_built("move_rates"); }
+  virtual void diag_move_rate(int) { not_built("move_rates"); }
   // tracked super-droplets (include/lcx_track.h): built for a single-device object
-  [[noreturn]] static void no_track() { throw std::runtime_error("libcloudph++: track on a multi-device object is not built"); }
-  virtual void track_enable(size_t, size_t, int) { no_track(); }
-  virtual void track_disable() { no_track(); }
-  virtual void track_select(const lcx_diag_clause_t *, int, const double *, size_t, size_t *) { no_track(); }
-  virtual void track_select_slots(const unsigned long long *, size_t, size_t *) { no_track(); }
-  virtual void track_sample() { no_track(); }
-  virtual void track_info(int *, size_t *, size_t *, size_t *, size_t *, unsigned long long *, int *, unsigned long long *) { no_track(); }
-  virtual void track_read(double *, size_t, size_t, unsigned long long *, double *, size_t, size_t *, bool, bool) { no_track(); }
+  virtual void track_enable(size_t, size_t, int) { not_built("track"); }
+  virtual void track_disable() { not_built("track"); }
+  virtual void track_select(const lcx_diag_clause_t *, int, const double *, size_t, size_t *) { not_built("track"); }
+  virtual void track_select_slots(const unsigned long long *, size_t, size_t *) { not_built("track"); }
+  virtual void track_sample() { not_built("track"); }
+  virtual void track_info(int *, size_t *, size_t *, size_t *, size_t *, unsigned long long *, int *, unsigned long long *) { not_built("track"); }
+  virtual void track_read(double *, size_t, size_t, unsigned long long *, double *, size_t, size_t *, bool, bool) { not_built("track"); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -297,6 +295,24 @@ template <class T> static RlxTables<T> rlx_make_tables(const lcx_opts_init_t &o)
   }
   return t;
 }
+
+// ---- one per-cell rate table: the storage and state behind lcx_coal_rates.h, lcx_cond_rates.h and lcx_move_rates.h alike ----
+// acc is [rows][n_cell] words of 8 bytes: row w holds unsigned 64-bit counts where bit w of count_rows is set, a double sum of m r^3 otherwise.
+// Particles zeroes it on enable and on a resetting read, reads it out as doubles at a row stride and hands out single rows through outbuf()
+// (its rt_* members); what feeds the rows, and their layout, belongs to the family.
+struct RateTable {
+  enum { MAX_THR = 4 };
+  const char *tag, *off;                             // for the error texts: the family's name, and what "... not enabled" calls the table
+  bool on = false;
+  int k = 0; double r_thr[MAX_THR] = {0, 0, 0, 0};   // the thresholds it was enabled with
+  int rows = 0; uint64_t count_rows = 0;
+  unsigned long long calls = 0;                      // what the family's info entry reports: launches or calls tallied since enable or the last reset
+  DevBuf<unsigned long long> acc; DevBuf<double> out; std::vector<double> host;      // (out, host: a read's staging on the device and on the host)
+  // count_rows of a layout that repeats n_per rows for each of k thresholds, one_thr being the mask of the rows of one threshold
+  static uint64_t per_thr(uint64_t one_thr, int n_per, int k) { uint64_t m = 0; for (int t = 0; t < k; ++t) m |= one_thr << (n_per * t); return m; }
+};
+static_assert(LCX_CDR_MAX_THR == RateTable::MAX_THR && LCX_MVR_MAX_THR == RateTable::MAX_THR, "the thresholds of a rate table");
+static_assert(LCX_CDR_PER_THR * LCX_CDR_MAX_THR + 1 <= 64 && LCX_MVR_PER_THR * LCX_MVR_MAX_THR <= 64 && LCX_CR_COUNT <= 64, "count_rows holds a bit per row");
 
 template <class real_t>
 struct Particles : IParticles {
@@ -1785,128 +1801,115 @@ struct Particles : IParticles {
     return !dbg(LCX_DBG_NO_COAL_SKIP) && n_emax > 0 && nphys > 0 && (vtc.formula == LCX_VT_BEARD77 || vtc.formula == LCX_VT_BEARD77FAST) &&
            !sort_deferred && (coal_ranks_owed_order() || coal_owes_unshuffled_cells());
   }
+  // ---- per-cell rate tables: what the collision, condensation and move rates below share (RateTable, above) ----
+  // (the lower bound of lcx_diag_wet_rng(r_thr, ...) in the object's real type: what a tally kernel compares rw2 with)
+  static T rt_lo(double r_thr) { double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, r_thr, r_thr, lo, hi); return T(lo); }
+  void rt_bounds(const RateTable &t, T *lo) const { for (int i = 0; i < t.k; ++i) lo[i] = rt_lo(t.r_thr[i]); }
+  [[noreturn]] static void rt_fail(const RateTable &t, const std::string &what) { throw lcx_error(std::string("libcloudph++: ") + t.tag + ": " + what); }
+  void rt_need(const RateTable &t, const char *what) const { if (!t.on) rt_fail(t, std::string(what) + " while " + t.off + " not enabled (lcx_" + t.tag + "_enable)"); }
+  void rt_zero(RateTable &t) { HIPCHK(hipMemsetAsync(t.acc.p, 0, size_t(t.rows) * ncell * sizeof(unsigned long long), st)); t.calls = 0; }
+  // 1 .. MAX_THR finite thresholds that increase strictly, as radii and as the bounds that the kernels compare with
+  void rt_check_thresholds(const RateTable &t, const double *r_thr, int n_thr, bool zero_ok) const
+  {
+    if (n_thr < 1 || n_thr > RateTable::MAX_THR) rt_fail(t, "n_thr = " + std::to_string(n_thr) + " is outside 1 .. " + std::to_string(int(RateTable::MAX_THR)));
+    if (!r_thr) rt_fail(t, "r_thr == NULL");
+    T lo_prev = T(0);
+    for (int i = 0; i < n_thr; ++i) {
+      if (!(zero_ok ? r_thr[i] >= 0 : r_thr[i] > 0) || !std::isfinite(r_thr[i]))
+        rt_fail(t, std::string("every threshold must be ") + (zero_ok ? "non-negative" : "positive") + " and finite");
+      if (i && !(r_thr[i] > r_thr[i - 1])) rt_fail(t, "the thresholds must be strictly increasing");
+      const T lo = rt_lo(r_thr[i]);
+      if (i && !(lo > lo_prev)) rt_fail(t, "the bounds r_thr^2 of thresholds " + std::to_string(i - 1) + " and " + std::to_string(i) +
+                                           " are not strictly increasing in the object's real type");
+      lo_prev = lo;
+    }
+  }
+  void rt_enable(RateTable &t, const double *r_thr, int n_thr, int rows, uint64_t count_rows)
+  {
+    const size_t n = size_t(rows) * ncell;
+    if (t.acc.p && t.acc.n < n) HIPCHK(hipStreamSynchronize(st));      // (a kernel still queued may read the rows that a larger K re-allocates)
+    t.k = n_thr; for (int i = 0; i < RateTable::MAX_THR; ++i) t.r_thr[i] = i < n_thr ? r_thr[i] : 0.;
+    t.rows = rows; t.count_rows = count_rows;
+    t.acc.alloc(n);
+    t.on = true;
+    rt_zero(t);
+  }
+  void rt_disable(RateTable &t)                          // (the family's scratch columns are released behind it: no kernel reads them any more)
+  {
+    t.on = false; t.k = t.rows = 0; t.calls = 0; for (double &r : t.r_thr) r = 0;
+    if (t.acc.p) { HIPCHK(hipStreamSynchronize(st)); t.acc.release(); t.out.release(); }
+  }
+  void rt_info(const RateTable &t, int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) const
+  {
+    if (enabled) *enabled = t.on ? 1 : 0;
+    if (n_thr) *n_thr = t.k;
+    if (r_thr) for (int i = 0; i < t.k; ++i) r_thr[i] = t.r_thr[i];
+    if (calls) *calls = t.calls;
+  }
+  // the whole table as doubles, out[w * stride + c]: on the stream the conversion, the copy to the host, the reset; one launch and one wait
+  void rt_read(RateTable &t, double *out, size_t stride, bool on_device, bool reset)
+  {
+    rt_need(t, "read");
+    if (!out) rt_fail(t, "out == NULL");
+    if (stride < ncell) rt_fail(t, "stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
+    if (!on_device) { t.out.alloc(size_t(t.rows) * ncell); t.host.resize(size_t(t.rows) * ncell); }
+    hipLaunchKernelGGL(k_rate_table_f64, dim3(nblk(ncell), t.rows), dim3(BS), 0, st, ncell, (const unsigned long long *)t.acc.p, t.count_rows,
+                       on_device ? out : t.out.p, on_device ? stride : ncell);
+    if (!on_device) HIPCHK(hipMemcpyAsync(t.host.data(), t.out.p, t.host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (reset) rt_zero(t);
+    sync();
+    if (!on_device) for (int w = 0; w < t.rows; ++w) memcpy(out + size_t(w) * stride, t.host.data() + size_t(w) * ncell, ncell * sizeof(double));
+  }
+  // one row into outbuf(), normalised as a diag_*_mom result (what: the entry's name, arg: what it calls the row, for the error texts)
+  void rt_diag(const RateTable &t, const char *what, const char *arg, int row)
+  {
+    rt_need(t, what);
+    if (!init_called) rt_fail(t, std::string(what) + " before init()");
+    if (row < 0 || row >= t.rows) rt_fail(t, std::string(arg) + " = " + std::to_string(row) + " is outside 0 .. " + std::to_string(t.rows - 1));
+    hipLaunchKernelGGL(k_rate_row_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(t.acc.p + size_t(row) * ncell),
+                       int(!((t.count_rows >> row) & 1)), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
+    sync();
+  }
   // ---- collision rates per cell (include/lcx_coal_rates.h): seven accumulators per cell, fed by the coalescence kernels' TALLY forms ----
   // While they are on, every coalescence launch is the TALLY form of the kernel it would have been (bound, early exit and all: a skipped pair is
   // one that cannot collide); off, nothing below is looked at and every launch is the one it was.
-  bool cr_on = false; double cr_r_thr = 0; unsigned long long cr_launches = 0;
-  DevBuf<unsigned long long> cr_acc; DevBuf<double> cr_out; std::vector<double> cr_host;
-  static constexpr unsigned CR_M3_ROWS = (1u << LCX_CR_ACNV_M3) | (1u << LCX_CR_ACCR_M3);
+  RateTable cr{"coal_rates", "the accumulators are"};
+  static constexpr uint64_t CR_N_ROWS = ((1ull << LCX_CR_COUNT) - 1) & ~((1ull << LCX_CR_ACNV_M3) | (1ull << LCX_CR_ACCR_M3));
   coal_tally_arg<T, true> cr_arg()                  // what a tallying launch is handed; counts the launch ("launches" of lcx_coal_rates_info)
   {
-    double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, cr_r_thr, cr_r_thr, lo, hi);       // (what lcx_diag_wet_rng(r_thr, ...) selects from)
-    ++cr_launches;
-    return coal_tally_arg<T, true>{cr_acc.p, ncell, T(lo)};
+    ++cr.calls;
+    return coal_tally_arg<T, true>{cr.acc.p, ncell, rt_lo(cr.r_thr[0])};
   }
-  void cr_zero() { HIPCHK(hipMemsetAsync(cr_acc.p, 0, size_t(LCX_CR_COUNT) * ncell * sizeof(unsigned long long), st)); cr_launches = 0; }
   void coal_rates_enable(double r_thr) override
   {
-    if (!(r_thr > 0) || !std::isfinite(r_thr)) throw lcx_error("libcloudph++: coal_rates: r_thr must be positive and finite");
-    cr_acc.alloc(size_t(LCX_CR_COUNT) * ncell);
-    cr_r_thr = r_thr; cr_on = true;
-    cr_zero();
+    if (!(r_thr > 0) || !std::isfinite(r_thr)) rt_fail(cr, "r_thr must be positive and finite");
+    rt_enable(cr, &r_thr, 1, LCX_CR_COUNT, CR_N_ROWS);
   }
-  void coal_rates_disable() override { cr_on = false; cr_r_thr = 0; cr_launches = 0; if (cr_acc.p) { HIPCHK(hipStreamSynchronize(st)); cr_acc.release(); cr_out.release(); } }
+  void coal_rates_disable() override { rt_disable(cr); }
   void coal_rates_info(int *enabled, double *r_thr, unsigned long long *launches) override
   {
-    if (enabled) *enabled = cr_on ? 1 : 0;
-    if (r_thr) *r_thr = cr_r_thr;
-    if (launches) *launches = cr_launches;
+    rt_info(cr, enabled, nullptr, nullptr, launches);
+    if (r_thr) *r_thr = cr.r_thr[0];                 // (0 while they are off)
   }
-  void cr_need(const char *what) const { if (!cr_on) throw lcx_error(std::string("libcloudph++: coal_rates: ") + what + " while the accumulators are not enabled (lcx_coal_rates_enable)"); }
-  void coal_rates_read(double *out, size_t stride, bool on_device, bool reset) override
-  {
-    cr_need("read");
-    if (!out) throw lcx_error("libcloudph++: coal_rates: out == NULL");
-    if (stride < ncell) throw lcx_error("libcloudph++: coal_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
-    const dim3 gr(nblk(ncell), LCX_CR_COUNT);
-    if (on_device) hipLaunchKernelGGL(k_coal_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cr_acc.p, CR_M3_ROWS, out, stride);
-    else {
-      cr_out.alloc(size_t(LCX_CR_COUNT) * ncell); cr_host.resize(size_t(LCX_CR_COUNT) * ncell);
-      hipLaunchKernelGGL(k_coal_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cr_acc.p, CR_M3_ROWS, cr_out.p, ncell);
-      HIPCHK(hipMemcpyAsync(cr_host.data(), cr_out.p, cr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (reset) cr_zero();
-    sync();
-    if (!on_device) for (int w = 0; w < LCX_CR_COUNT; ++w) memcpy(out + size_t(w) * stride, cr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
-  }
-  void diag_coal_rate(int which) override
-  {
-    cr_need("diag_coal_rate");
-    if (!init_called) throw lcx_error("libcloudph++: coal_rates: diag_coal_rate before init()");
-    if (which < 0 || which >= LCX_CR_COUNT) throw lcx_error("libcloudph++: coal_rates: which = " + std::to_string(which) + " is outside 0 .. " + std::to_string(LCX_CR_COUNT - 1));
-    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(cr_acc.p + size_t(which) * ncell),
-                       int((CR_M3_ROWS >> which) & 1u), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
-    sync();
-  }
+  void coal_rates_read(double *out, size_t stride, bool on_device, bool reset) override { rt_read(cr, out, stride, on_device, reset); }
+  void diag_coal_rate(int which) override { rt_diag(cr, "diag_coal_rate", "which", which); }
   // ---- condensation rates per cell (include/lcx_cond_rates.h): 5 K + 1 rows per cell, fed by a pass of its own around step_cond's condensation ----
   // While they are on, step_cond copies rw2 into a scratch column ahead of its first condensation launch (cdr_before) and launches k_cond_rates
   // behind the last substep (cdr_tally): two launches more, and no condensation kernel is another one.  Storage slots do not move in between
   // (reorder_storage and the compaction belong to the move and post_copy), so slot i of the column is slot i of A.rw2.  Off, nothing below is
   // looked at and nothing is allocated.
-  bool cdr_on = false; int cdr_k = 0; double cdr_r_thr[LCX_CDR_MAX_THR] = {0, 0, 0, 0}; unsigned long long cdr_calls = 0;
-  DevBuf<unsigned long long> cdr_acc; DevBuf<T> cdr_rw2_before; DevBuf<double> cdr_out; std::vector<double> cdr_host;
-  int cdr_rows() const { return LCX_CDR_PER_THR * cdr_k + 1; }
-  void cdr_zero() { HIPCHK(hipMemsetAsync(cdr_acc.p, 0, size_t(cdr_rows()) * ncell * sizeof(unsigned long long), st)); cdr_calls = 0; }
+  RateTable cdr{"cond_rates", "the tally is"};
+  DevBuf<T> cdr_rw2_before;
+  static constexpr uint64_t CDR_N_ROWS = (1ull << LCX_CDR_UP_N) | (1ull << LCX_CDR_DOWN_N);       // (of one threshold; the last row, TOTAL_DM3, is a sum)
   void cond_rates_enable(const double *r_thr, int n_thr) override
   {
-    if (n_thr < 1 || n_thr > LCX_CDR_MAX_THR) throw lcx_error("libcloudph++: cond_rates: n_thr = " + std::to_string(n_thr) + " is outside 1 .. " + std::to_string(int(LCX_CDR_MAX_THR)));
-    if (!r_thr) throw lcx_error("libcloudph++: cond_rates: r_thr == NULL");
-    T lo_prev = T(0);
-    for (int t = 0; t < n_thr; ++t) {
-      if (!(r_thr[t] > 0) || !std::isfinite(r_thr[t])) throw lcx_error("libcloudph++: cond_rates: every threshold must be positive and finite");
-      if (t && !(r_thr[t] > r_thr[t - 1])) throw lcx_error("libcloudph++: cond_rates: the thresholds must be strictly increasing");
-      double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, r_thr[t], r_thr[t], lo, hi);
-      if (t && !(T(lo) > lo_prev)) throw lcx_error("libcloudph++: cond_rates: the bounds r_thr^2 of thresholds " + std::to_string(t - 1) + " and " + std::to_string(t) +
-                                                  " are not strictly increasing in the object's real type");
-      lo_prev = T(lo);
-    }
-    if (cdr_acc.p) HIPCHK(hipStreamSynchronize(st));             // (a kernel still queued may read the rows that a larger K re-allocates)
-    cdr_k = n_thr; for (int t = 0; t < LCX_CDR_MAX_THR; ++t) cdr_r_thr[t] = t < n_thr ? r_thr[t] : 0.;
-    cdr_acc.alloc(size_t(cdr_rows()) * ncell);
-    cdr_on = true;
-    cdr_zero();
+    rt_check_thresholds(cdr, r_thr, n_thr, false);
+    rt_enable(cdr, r_thr, n_thr, LCX_CDR_PER_THR * n_thr + 1, RateTable::per_thr(CDR_N_ROWS, LCX_CDR_PER_THR, n_thr));
   }
-  void cond_rates_disable() override
-  {
-    cdr_on = false; cdr_k = 0; cdr_calls = 0; for (double &r : cdr_r_thr) r = 0;
-    if (cdr_acc.p || cdr_rw2_before.p) { HIPCHK(hipStreamSynchronize(st)); cdr_acc.release(); cdr_rw2_before.release(); cdr_out.release(); }
-  }
-  void cond_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override
-  {
-    if (enabled) *enabled = cdr_on ? 1 : 0;
-    if (n_thr) *n_thr = cdr_k;
-    if (r_thr) for (int t = 0; t < cdr_k; ++t) r_thr[t] = cdr_r_thr[t];
-    if (calls) *calls = cdr_calls;
-  }
-  void cdr_need(const char *what) const { if (!cdr_on) throw lcx_error(std::string("libcloudph++: cond_rates: ") + what + " while the tally is not enabled (lcx_cond_rates_enable)"); }
-  void cond_rates_read(double *out, size_t stride, bool on_device, bool reset) override
-  {
-    cdr_need("read");
-    if (!out) throw lcx_error("libcloudph++: cond_rates: out == NULL");
-    if (stride < ncell) throw lcx_error("libcloudph++: cond_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
-    const int rows = cdr_rows();
-    const dim3 gr(nblk(ncell), rows);
-    if (on_device) hipLaunchKernelGGL(k_cond_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cdr_acc.p, cdr_k, out, stride);
-    else {
-      cdr_out.alloc(size_t(rows) * ncell); cdr_host.resize(size_t(rows) * ncell);
-      hipLaunchKernelGGL(k_cond_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)cdr_acc.p, cdr_k, cdr_out.p, ncell);
-      HIPCHK(hipMemcpyAsync(cdr_host.data(), cdr_out.p, cdr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (reset) cdr_zero();
-    sync();
-    if (!on_device) for (int w = 0; w < rows; ++w) memcpy(out + size_t(w) * stride, cdr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
-  }
-  void diag_cond_rate(int row) override
-  {
-    cdr_need("diag_cond_rate");
-    if (!init_called) throw lcx_error("libcloudph++: cond_rates: diag_cond_rate before init()");
-    if (row < 0 || row >= cdr_rows()) throw lcx_error("libcloudph++: cond_rates: row = " + std::to_string(row) + " is outside 0 .. " + std::to_string(cdr_rows() - 1));
-    const int which = row % LCX_CDR_PER_THR;
-    const bool is_n = row < LCX_CDR_PER_THR * cdr_k && (which == LCX_CDR_UP_N || which == LCX_CDR_DOWN_N);
-    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(cdr_acc.p + size_t(row) * ncell),
-                       int(!is_n), (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
-    sync();
-  }
+  void cond_rates_disable() override { rt_disable(cdr); cdr_rw2_before.release(); }
+  void cond_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override { rt_info(cdr, enabled, n_thr, r_thr, calls); }
+  void cond_rates_read(double *out, size_t stride, bool on_device, bool reset) override { rt_read(cdr, out, stride, on_device, reset); }
+  void diag_cond_rate(int row) override { rt_diag(cdr, "diag_cond_rate", "row", row); }
   // step_cond, ahead of the first condensation launch: rw2 as stored, into the scratch column (allocated here: the capacity is not known before init)
   void cdr_before()
   {
@@ -1917,85 +1920,35 @@ struct Particles : IParticles {
   // step_cond, behind the last substep
   template <int K> void cdr_launch()
   {
-    cond_rates_arg<T, K> a{A.n.p, cdr_rw2_before.p, A.rw2.p, ijk.p, cdr_acc.p, ncell, {}};
-    for (int t = 0; t < K; ++t) { double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, cdr_r_thr[t], cdr_r_thr[t], lo, hi); a.lo[t] = T(lo); }
+    cond_rates_arg<T, K> a{A.n.p, cdr_rw2_before.p, A.rw2.p, ijk.p, cdr.acc.p, ncell, {}};
+    rt_bounds(cdr, a.lo);
     hipLaunchKernelGGL((k_cond_rates<T, K>), dim3(nblk(nphys)), dim3(BS), 0, st, nphys, a);
   }
   void cdr_tally()
   {
-    ++cdr_calls;
+    ++cdr.calls;
     if (!nphys) return;
     Range r(this, "cond_rates");
-    switch (cdr_k) { case 1: cdr_launch<1>(); break; case 2: cdr_launch<2>(); break; case 3: cdr_launch<3>(); break; default: cdr_launch<4>(); }
+    switch (cdr.k) { case 1: cdr_launch<1>(); break; case 2: cdr_launch<2>(); break; case 3: cdr_launch<3>(); break; default: cdr_launch<4>(); }
   }
   // ---- move rates per cell (include/lcx_move_rates.h): 10 K rows per cell, fed by a pass of its own around step_async's move ----
   // While they are on, step_async copies ijk and n into two scratch columns ahead of the move (mvr_before: the fused move overwrites ijk in
   // place and every move zeroes the n of what it removes) and launches k_move_rates right behind it (mvr_tally), ahead of everything that
   // appends, compacts, re-orders or re-indexes: one launch more, and no k_move instantiation is another one.  Off, nothing below is looked
   // at and nothing is allocated.
-  bool mvr_on = false; int mvr_k = 0; double mvr_r_thr[LCX_MVR_MAX_THR] = {0, 0, 0, 0}; unsigned long long mvr_calls = 0;
-  DevBuf<unsigned long long> mvr_acc; DevBuf<uint32_t> mvr_ijk_before; DevBuf<n_t> mvr_n_before; DevBuf<double> mvr_out; std::vector<double> mvr_host;
-  int mvr_rows() const { return LCX_MVR_PER_THR * mvr_k; }
-  void mvr_zero() { HIPCHK(hipMemsetAsync(mvr_acc.p, 0, size_t(mvr_rows()) * ncell * sizeof(unsigned long long), st)); mvr_calls = 0; }
+  RateTable mvr{"move_rates", "the tally is"};
+  DevBuf<uint32_t> mvr_ijk_before; DevBuf<n_t> mvr_n_before;
+  static constexpr uint64_t MVR_N_ROWS = (1ull << LCX_MVR_IN_N) | (1ull << LCX_MVR_OUT_N) | (1ull << LCX_MVR_DOWN_N) | (1ull << LCX_MVR_UP_N) | (1ull << LCX_MVR_PRECIP_N);
   void move_rates_enable(const double *r_thr, int n_thr) override
   {
     if (distmem()) throw lcx_error("libcloudph++: move_rates on a decomposed domain is not built");
-    if (n_thr < 1 || n_thr > LCX_MVR_MAX_THR) throw lcx_error("libcloudph++: move_rates: n_thr = " + std::to_string(n_thr) + " is outside 1 .. " + std::to_string(int(LCX_MVR_MAX_THR)));
-    if (!r_thr) throw lcx_error("libcloudph++: move_rates: r_thr == NULL");
-    T lo_prev = T(0);
-    for (int t = 0; t < n_thr; ++t) {
-      if (!(r_thr[t] >= 0) || !std::isfinite(r_thr[t])) throw lcx_error("libcloudph++: move_rates: every threshold must be non-negative and finite");
-      if (t && !(r_thr[t] > r_thr[t - 1])) throw lcx_error("libcloudph++: move_rates: the thresholds must be strictly increasing");
-      double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, r_thr[t], r_thr[t], lo, hi);
-      if (t && !(T(lo) > lo_prev)) throw lcx_error("libcloudph++: move_rates: the bounds r_thr^2 of thresholds " + std::to_string(t - 1) + " and " + std::to_string(t) +
-                                                  " are not strictly increasing in the object's real type");
-      lo_prev = T(lo);
-    }
-    if (mvr_acc.p) HIPCHK(hipStreamSynchronize(st));             // (a kernel still queued may read the rows that a larger K re-allocates)
-    mvr_k = n_thr; for (int t = 0; t < LCX_MVR_MAX_THR; ++t) mvr_r_thr[t] = t < n_thr ? r_thr[t] : 0.;
-    mvr_acc.alloc(size_t(mvr_rows()) * ncell);
-    mvr_on = true;
-    mvr_zero();
+    rt_check_thresholds(mvr, r_thr, n_thr, true);
+    rt_enable(mvr, r_thr, n_thr, LCX_MVR_PER_THR * n_thr, RateTable::per_thr(MVR_N_ROWS, LCX_MVR_PER_THR, n_thr));
   }
-  void move_rates_disable() override
-  {
-    mvr_on = false; mvr_k = 0; mvr_calls = 0; for (double &r : mvr_r_thr) r = 0;
-    if (mvr_acc.p || mvr_ijk_before.p) { HIPCHK(hipStreamSynchronize(st)); mvr_acc.release(); mvr_ijk_before.release(); mvr_n_before.release(); mvr_out.release(); }
-  }
-  void move_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override
-  {
-    if (enabled) *enabled = mvr_on ? 1 : 0;
-    if (n_thr) *n_thr = mvr_k;
-    if (r_thr) for (int t = 0; t < mvr_k; ++t) r_thr[t] = mvr_r_thr[t];
-    if (calls) *calls = mvr_calls;
-  }
-  void mvr_need(const char *what) const { if (!mvr_on) throw lcx_error(std::string("libcloudph++: move_rates: ") + what + " while the tally is not enabled (lcx_move_rates_enable)"); }
-  void move_rates_read(double *out, size_t stride, bool on_device, bool reset) override
-  {
-    mvr_need("read");
-    if (!out) throw lcx_error("libcloudph++: move_rates: out == NULL");
-    if (stride < ncell) throw lcx_error("libcloudph++: move_rates: stride (" + std::to_string(stride) + ") < n_cell (" + std::to_string(ncell) + ")");
-    const int rows = mvr_rows();
-    const dim3 gr(nblk(ncell), rows);
-    if (on_device) hipLaunchKernelGGL(k_move_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)mvr_acc.p, out, stride);
-    else {
-      mvr_out.alloc(size_t(rows) * ncell); mvr_host.resize(size_t(rows) * ncell);
-      hipLaunchKernelGGL(k_move_rates_f64, gr, dim3(BS), 0, st, ncell, (const unsigned long long *)mvr_acc.p, mvr_out.p, ncell);
-      HIPCHK(hipMemcpyAsync(mvr_host.data(), mvr_out.p, mvr_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (reset) mvr_zero();
-    sync();
-    if (!on_device) for (int w = 0; w < rows; ++w) memcpy(out + size_t(w) * stride, mvr_host.data() + size_t(w) * ncell, ncell * sizeof(double));
-  }
-  void diag_move_rate(int row) override
-  {
-    mvr_need("diag_move_rate");
-    if (!init_called) throw lcx_error("libcloudph++: move_rates: diag_move_rate before init()");
-    if (row < 0 || row >= mvr_rows()) throw lcx_error("libcloudph++: move_rates: row = " + std::to_string(row) + " is outside 0 .. " + std::to_string(mvr_rows() - 1));
-    hipLaunchKernelGGL(k_coal_rate_out<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const unsigned long long *)(mvr_acc.p + size_t(row) * ncell),
-                       row & 1, (const T *)dv.p, (const T *)rhod.p, int(n_dims > 0), count_mom.p);
-    sync();
-  }
+  void move_rates_disable() override { rt_disable(mvr); mvr_ijk_before.release(); mvr_n_before.release(); }
+  void move_rates_info(int *enabled, int *n_thr, double *r_thr, unsigned long long *calls) override { rt_info(mvr, enabled, n_thr, r_thr, calls); }
+  void move_rates_read(double *out, size_t stride, bool on_device, bool reset) override { rt_read(mvr, out, stride, on_device, reset); }
+  void diag_move_rate(int row) override { rt_diag(mvr, "diag_move_rate", "row", row); }
   // step_async, ahead of the move: ijk and n as stored, into the scratch columns (allocated here: the capacity is not known before init)
   void mvr_before()
   {
@@ -2008,16 +1961,16 @@ struct Particles : IParticles {
   template <int K> void mvr_launch(size_t n_moved, bool fused)
   {
     move_rates_arg<T, K> a{mvr_n_before.p, A.n.p, mvr_ijk_before.p, fused ? (const uint32_t *)ijk.p : (const uint32_t *)nullptr, A.rw2.p, A.x.p, A.y.p, A.z.p,
-                           mvr_acc.p, ncell, g, T(o.x0), T(o.x1), T(o.y0), T(o.y1), T(o.z0), T(o.z1), int(o.open_side_walls), int(o.periodic_topbot_walls), {}};
-    for (int t = 0; t < K; ++t) { double lo, hi; lcx::diag::rng_bounds(LCX_DIAG_SEL_WET, mvr_r_thr[t], mvr_r_thr[t], lo, hi); a.lo[t] = T(lo); }
+                           mvr.acc.p, ncell, g, T(o.x0), T(o.x1), T(o.y0), T(o.y1), T(o.z0), T(o.z1), int(o.open_side_walls), int(o.periodic_topbot_walls), {}};
+    rt_bounds(mvr, a.lo);
     hipLaunchKernelGGL((k_move_rates<T, K>), dim3(nblk(n_moved)), dim3(BS), 0, st, n_moved, a);
   }
   void mvr_tally(size_t n_moved, bool fused)
   {
-    ++mvr_calls;
+    ++mvr.calls;
     if (!n_moved || n_dims == 0) return;
     Range r(this, "move_rates");
-    switch (mvr_k) { case 1: mvr_launch<1>(n_moved, fused); break; case 2: mvr_launch<2>(n_moved, fused); break; case 3: mvr_launch<3>(n_moved, fused); break; default: mvr_launch<4>(n_moved, fused); }
+    switch (mvr.k) { case 1: mvr_launch<1>(n_moved, fused); break; case 2: mvr_launch<2>(n_moved, fused); break; case 3: mvr_launch<3>(n_moved, fused); break; default: mvr_launch<4>(n_moved, fused); }
   }
   // ---- tracked super-droplets (include/lcx_track.h): one more ext column holding k + 1, the slot of every index, a sample buffer ----
   // The column is the LAST one (nothing else adds columns after construction), so enabling and disabling are n_ext + 1 and n_ext - 1 and
@@ -2293,7 +2246,7 @@ struct Particles : IParticles {
         else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, false, TL>); else launch(k_coal_ranked<T, false, true, false, TL>); }
         else if (coal_marks_dead) launch(k_coal_ranked<T, true, false, false, TL>); else launch(k_coal_ranked<T, false, false, false, TL>);
       };
-      if (cr_on) launch_all(std::true_type{}); else launch_all(std::false_type{});
+      if (cr.on) launch_all(std::true_type{}); else launch_all(std::false_type{});
       if (ska.cmax && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
         if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 128 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
         skip_sample_n = ska.cnt ? 4 : 128;
@@ -2314,7 +2267,7 @@ struct Particles : IParticles {
     };
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
     const bool production = tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead;
-    if (cr_on) {                                        // the same three kernels, feeding the collision rates' accumulators
+    if (cr.on) {                                        // the same three kernels, feeding the collision rates' accumulators
       const coal_tally_arg<T, true> ta = cr_arg();
       auto tally = [&](auto kern, bool need_col = true) {
         hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
@@ -3124,7 +3077,7 @@ struct Particles : IParticles {
     if (ix_ict >= 0 && nphys)                                                            // update_incloud_time, particles_step.ipp:180-181
       hipLaunchKernelGGL(k_incloud_time<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, ijk.p, A.rd3.p, A.kpa.p, A.rw2.p, Tk.p, T(dt), A.ext[ix_ict].p);
     if (opts.cond) {
-      if (cdr_on) cdr_before();                    // (include/lcx_cond_rates.h: rw2 as stored ahead of the first condensation launch)
+      if (cdr.on) cdr_before();                    // (include/lcx_cond_rates.h: rw2 as stored ahead of the first condensation launch)
       // (a measurement switch that names one of the per-substep kernels gets that kernel)
       constexpr unsigned per_substep_variants = LCX_DBG_COND_NO_FUSED_SUBSTEPS | LCX_DBG_COND_FOLD | LCX_DBG_COND_WQ | LCX_DBG_COND_BUDGET | LCX_DBG_COND_PROBE |
                                                 LCX_DBG_COND_LEAN_R3 | LCX_DBG_FINISH_STAGED | LCX_DBG_COND_NO_FOLD;
@@ -3139,7 +3092,7 @@ struct Particles : IParticles {
         cond_substep(opts.RH_max, step, opts.turb_cond);                                 // (hskpng_mfp at substep 0 and hskpng_Tpr inside)
       }
       sstp_save();
-      if (cdr_on) cdr_tally();                     // (behind the last substep, whichever kernels ran it)
+      if (cdr.on) cdr_tally();                     // (behind the last substep, whichever kernels ran it)
       if (!chem_now) { Range r(this, "sync_out"); sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); flush_sync_jobs(); }
     }
     if (chem_now) {                                // (after condensation, ahead of the results going out: particles_step.ipp:269-327)
@@ -3232,10 +3185,10 @@ struct Particles : IParticles {
     // an order still owed: void where the step ends in the fused move and its re-sort with nothing in between that reads the old order (the
     // move writes the next sort's arrival ranks); made now otherwise
     if (rank_owed) { if (fused && !distmem() && !src_now && !rlx_now) rank_owed = false; else pay_rank(); }
-    if (mvr_on) mvr_before();                      // (include/lcx_move_rates.h: ijk and n as stored ahead of the move)
+    if (mvr.on) mvr_before();                      // (include/lcx_move_rates.h: ijk and n as stored ahead of the move)
     const size_t n_moved = nphys;
     move(opts.adve, opts.sedi, opts.subs, true, fused);
-    if (mvr_on) mvr_tally(n_moved, fused);         // (ahead of whatever appends, compacts, re-orders or re-indexes)
+    if (mvr.on) mvr_tally(n_moved, fused);         // (ahead of whatever appends, compacts, re-orders or re-indexes)
     if (n_chem_pud) chem_puddle_add(n_chem_pud);
     hold_big_list = false;
     adve_scheme = o.adve_scheme;

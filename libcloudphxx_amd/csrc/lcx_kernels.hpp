@@ -3037,22 +3037,26 @@ __global__ void k_coal_kappa(size_t n_part, const uint32_t *sorted_id, const T *
   }
   if (na_ge_nb) kpa[b] = kb; else kpa[a] = ka;
 }
-// lcx_diag_coal_rate: one accumulator row as the object's real type, normalised as a diag_*_mom result (by dv, then by rhod; a parcel is not divided)
+// The per-cell rate tables of the collision, condensation and move rates: [rows][n_cell] words of 8 bytes, a row holding
+// unsigned 64-bit counts or a double sum of m r^3.
+// lcx_diag_coal_rate, lcx_diag_cond_rate, lcx_diag_move_rate: one row as the object's real type, normalised as a diag_*_mom result (by dv, then by
+// rhod; a parcel is not divided)
 template <class T>
-__global__ void k_coal_rate_out(size_t n_cell, const unsigned long long *row, int is_m3, const T *dv, const T *rhod, int specific, T *out)
+__global__ void k_rate_row_out(size_t n_cell, const unsigned long long *row, int is_m3, const T *dv, const T *rhod, int specific, T *out)
 {
   const size_t c = gid(); if (c >= n_cell) return;
   T v = is_m3 ? T(reinterpret_cast<const double *>(row)[c]) : T(double(row[c]));
   if (specific) { v = v / dv[c]; v = v / rhod[c]; }
   out[c] = v;
 }
-// lcx_coal_rates_read: the [LCX_CR_COUNT][n_cell] block as doubles (the number rows converted), out[w * stride + c]
-__global__ void k_coal_rates_f64(size_t n_cell, const unsigned long long *acc, unsigned m3_rows, double *out, size_t stride)
+// lcx_coal_rates_read, lcx_cond_rates_read, lcx_move_rates_read: the whole table as doubles, out[w * stride + c]; blockIdx.y is the row w, and it is
+// converted where bit w of count_rows is set (up to 40 rows: a 64-bit mask)
+__global__ void k_rate_table_f64(size_t n_cell, const unsigned long long *acc, unsigned long long count_rows, double *out, size_t stride)
 {
   const size_t c = gid(); if (c >= n_cell) return;
   const unsigned w = blockIdx.y;
   const unsigned long long *row = acc + size_t(w) * n_cell;
-  out[size_t(w) * stride + c] = (m3_rows >> w) & 1u ? reinterpret_cast<const double *>(row)[c] : double(row[c]);
+  out[size_t(w) * stride + c] = (count_rows >> w) & 1ull ? double(row[c]) : reinterpret_cast<const double *>(row)[c];
 }
 
 // Condensation rates (include/lcx_cond_rates.h): what one step_cond did to every droplet relative to K thresholds, from rw2 as it
@@ -3114,16 +3118,6 @@ __global__ void __launch_bounds__(BS) k_cond_rates(size_t n_part, const cond_rat
     if (__ballot(up)) { add_n(LCX_CDR_PER_THR * t + LCX_CDR_UP_N, up ? mu : 0ull); add_m3(LCX_CDR_PER_THR * t + LCX_CDR_UP_M3, up ? m * c1 : 0.); }
     if (__ballot(down)) { add_n(LCX_CDR_PER_THR * t + LCX_CDR_DOWN_N, down ? mu : 0ull); add_m3(LCX_CDR_PER_THR * t + LCX_CDR_DOWN_M3, down ? m * c0 : 0.); }
   }
-}
-// lcx_cond_rates_read: the [5 K + 1][n_cell] block as doubles (the two number rows of every threshold converted), out[row * stride + c]
-__global__ void k_cond_rates_f64(size_t n_cell, const unsigned long long *acc, int n_thr, double *out, size_t stride)
-{
-  const size_t c = gid(); if (c >= n_cell) return;
-  const unsigned w = blockIdx.y;
-  const unsigned which = w % unsigned(LCX_CDR_PER_THR);
-  const bool is_n = int(w) < LCX_CDR_PER_THR * n_thr && (which == LCX_CDR_UP_N || which == LCX_CDR_DOWN_N);
-  const unsigned long long *row = acc + size_t(w) * n_cell;
-  out[size_t(w) * stride + c] = is_n ? double(row[c]) : reinterpret_cast<const double *>(row)[c];
 }
 
 // Move rates (include/lcx_move_rates.h): what the one move of a step_async did to every droplet relative to K thresholds, from
@@ -3243,14 +3237,6 @@ __global__ void __launch_bounds__(BS) k_move_rates(size_t n_part, const move_rat
   mvr_add<K>(a.acc, a.n_cell, LCX_MVR_DOWN_N, c0, moved && down, kt, mu, mr3);
   mvr_add<K>(a.acc, a.n_cell, LCX_MVR_UP_N, c0, moved && up, kt, mu, mr3);
   mvr_add<K>(a.acc, a.n_cell, LCX_MVR_PRECIP_N, cp, moved && cp != DEAD_CELL, kt, mu, mr3);
-}
-// lcx_move_rates_read: the [10 K][n_cell] block as doubles (the even rows are numbers and converted), out[row * stride + c]
-__global__ void k_move_rates_f64(size_t n_cell, const unsigned long long *acc, double *out, size_t stride)
-{
-  const size_t c = gid(); if (c >= n_cell) return;
-  const unsigned w = blockIdx.y;
-  const unsigned long long *row = acc + size_t(w) * n_cell;
-  out[size_t(w) * stride + c] = w & 1u ? reinterpret_cast<const double *>(row)[c] : double(row[c]);
 }
 
 // ============================================================================================

@@ -318,20 +318,65 @@ def diag_batch_check(reqs, lib=None):
         raise RuntimeError(lib.lcx_last_error().decode())
 
 
+# ---- per-cell rate tables: what the collision, condensation and move rates below share
+def _rates_out(tag, out, n_rows, n_cell):
+    """(address, row stride in doubles, on_device) of an output array of a rate table: (n_rows, n_cell) doubles with unit stride along
+    cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
+    if len(out.shape) != 2 or out.shape[0] != n_rows or out.shape[1] != n_cell:
+        raise ValueError("libcloudph++: %s: out must be 2-D, (%d, n_cell)" % (tag, n_rows))
+    if isinstance(out, DeviceArray):
+        ptr, strides = out.ptr, out.strides
+    else:
+        if out.dtype != np.float64:
+            raise ValueError("libcloudph++: %s: out must hold float64" % tag)
+        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
+            raise ValueError("libcloudph++: %s: unsupported strides" % tag)
+        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
+    if n_cell > 1 and strides[1] != 1:
+        raise ValueError("libcloudph++: %s: out must have unit stride along cells" % tag)
+    if strides[0] < n_cell:
+        raise ValueError("libcloudph++: %s: out's row stride is below n_cell" % tag)
+    return ptr, strides[0], isinstance(out, DeviceArray)
+
+
+def _rates_thresholds(tag, r_thr, n_max, zero_ok):
+    """the thresholds as an enable entry takes them, from a scalar or a sequence: 1 .. n_max finite, strictly increasing radii"""
+    r = [float(x) for x in np.atleast_1d(np.asarray(r_thr, dtype=np.float64)).ravel()]
+    if not 1 <= len(r) <= n_max:
+        raise ValueError("libcloudph++: %s: n_thr = %d is outside 1 .. %d" % (tag, len(r), n_max))
+    if not all((x >= 0 if zero_ok else x > 0) and np.isfinite(x) for x in r):
+        raise ValueError("libcloudph++: %s: every threshold must be %s and finite" % (tag, "non-negative" if zero_ok else "positive"))
+    if any(b <= a for a, b in zip(r, r[1:])):
+        raise ValueError("libcloudph++: %s: the thresholds must be strictly increasing" % tag)
+    return r
+
+
+def _rate_index(tag, names, name, t=0, n_thr=1, total=None, noun="row", arg="row"):
+    """the row of a name of `names` at threshold t (or of the trailing row `total`), or of a row number, among len(names) n_thr rows
+    (and that one)"""
+    n_rows = len(names) * n_thr + (total is not None)
+    if isinstance(name, str):
+        if name.lower() == total:
+            return n_rows - 1
+        if name.lower() not in names:
+            raise ValueError("libcloudph++: %s: unknown %s %r (one of %s)" % (tag, noun, name, ", ".join(names + ((total,) if total else ()))))
+        t = int(t)
+        if not 0 <= t < n_thr:
+            raise ValueError("libcloudph++: %s: t = %d is outside 0 .. %d" % (tag, t, n_thr - 1))
+        return len(names) * t + names.index(name.lower())
+    w = int(name)
+    if not 0 <= w < n_rows:
+        raise ValueError("libcloudph++: %s: %s = %d is outside 0 .. %d" % (tag, arg, w, n_rows - 1))
+    return w
+
+
 # ---- collision rates per cell (include/lcx_coal_rates.h)
 COAL_RATES = ("acnv_m3", "acnv_nc", "acnv_nr", "accr_m3", "accr_nc", "self_cloud_n", "self_rain_n")     # enum LCX_CR_*, in its order
 
 
 def coal_rate_index(name):
     """LCX_CR_* of an accumulator's name (one of COAL_RATES, any letter case) or of its number"""
-    if isinstance(name, str):
-        if name.lower() not in COAL_RATES:
-            raise ValueError("libcloudph++: coal_rates: unknown accumulator %r (one of %s)" % (name, ", ".join(COAL_RATES)))
-        return COAL_RATES.index(name.lower())
-    w = int(name)
-    if not 0 <= w < len(COAL_RATES):
-        raise ValueError("libcloudph++: coal_rates: which = %d is outside 0 .. %d" % (w, len(COAL_RATES) - 1))
-    return w
+    return _rate_index("coal_rates", COAL_RATES, name, noun="accumulator", arg="which")
 
 
 def coal_rates_threshold(r_thr):
@@ -343,23 +388,8 @@ def coal_rates_threshold(r_thr):
 
 
 def coal_rates_out(out, n_cell):
-    """(address, row stride in doubles, on_device) of an output array of coal_rates: (len(COAL_RATES), n_cell) doubles with unit stride
-    along cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
-    if len(out.shape) != 2 or out.shape[0] != len(COAL_RATES) or out.shape[1] != n_cell:
-        raise ValueError("libcloudph++: coal_rates: out must be 2-D, (%d, n_cell)" % len(COAL_RATES))
-    if isinstance(out, DeviceArray):
-        ptr, strides = out.ptr, out.strides
-    else:
-        if out.dtype != np.float64:
-            raise ValueError("libcloudph++: coal_rates: out must hold float64")
-        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
-            raise ValueError("libcloudph++: coal_rates: unsupported strides")
-        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
-    if n_cell > 1 and strides[1] != 1:
-        raise ValueError("libcloudph++: coal_rates: out must have unit stride along cells")
-    if strides[0] < n_cell:
-        raise ValueError("libcloudph++: coal_rates: out's row stride is below n_cell")
-    return ptr, strides[0], isinstance(out, DeviceArray)
+    """(address, row stride in doubles, on_device) of an output array of coal_rates: (len(COAL_RATES), n_cell), see _rates_out"""
+    return _rates_out("coal_rates", out, len(COAL_RATES), n_cell)
 
 
 # ---- condensation rates per cell (include/lcx_cond_rates.h)
@@ -370,53 +400,17 @@ COND_RATES_TOTAL = "total_dm3"                                       # the last 
 
 def cond_rates_thresholds(r_thr):
     """the thresholds as lcx_cond_rates_enable takes them, from a scalar or a sequence: 1 .. 4 positive, finite, strictly increasing radii"""
-    r = [float(x) for x in np.atleast_1d(np.asarray(r_thr, dtype=np.float64)).ravel()]
-    if not 1 <= len(r) <= COND_RATES_MAX_THR:
-        raise ValueError("libcloudph++: cond_rates: n_thr = %d is outside 1 .. %d" % (len(r), COND_RATES_MAX_THR))
-    if not all(x > 0 and np.isfinite(x) for x in r):
-        raise ValueError("libcloudph++: cond_rates: every threshold must be positive and finite")
-    if any(b <= a for a, b in zip(r, r[1:])):
-        raise ValueError("libcloudph++: cond_rates: the thresholds must be strictly increasing")
-    return r
+    return _rates_thresholds("cond_rates", r_thr, COND_RATES_MAX_THR, False)
 
 
 def cond_rate_index(name, t=0, n_thr=COND_RATES_MAX_THR):
     """the row of a name of COND_RATES at threshold t (or of "total_dm3"), or of a row number, among 5 n_thr + 1 rows"""
-    n_rows = len(COND_RATES) * n_thr + 1
-    if isinstance(name, str):
-        if name.lower() == COND_RATES_TOTAL:
-            return n_rows - 1
-        if name.lower() not in COND_RATES:
-            raise ValueError("libcloudph++: cond_rates: unknown row %r (one of %s, %s)" % (name, ", ".join(COND_RATES), COND_RATES_TOTAL))
-        t = int(t)
-        if not 0 <= t < n_thr:
-            raise ValueError("libcloudph++: cond_rates: t = %d is outside 0 .. %d" % (t, n_thr - 1))
-        return len(COND_RATES) * t + COND_RATES.index(name.lower())
-    w = int(name)
-    if not 0 <= w < n_rows:
-        raise ValueError("libcloudph++: cond_rates: row = %d is outside 0 .. %d" % (w, n_rows - 1))
-    return w
+    return _rate_index("cond_rates", COND_RATES, name, t, n_thr, total=COND_RATES_TOTAL)
 
 
 def cond_rates_out(out, n_thr, n_cell):
-    """(address, row stride in doubles, on_device) of an output array of cond_rates: (5 n_thr + 1, n_cell) doubles with unit stride
-    along cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
-    n_rows = len(COND_RATES) * n_thr + 1
-    if len(out.shape) != 2 or out.shape[0] != n_rows or out.shape[1] != n_cell:
-        raise ValueError("libcloudph++: cond_rates: out must be 2-D, (%d, n_cell)" % n_rows)
-    if isinstance(out, DeviceArray):
-        ptr, strides = out.ptr, out.strides
-    else:
-        if out.dtype != np.float64:
-            raise ValueError("libcloudph++: cond_rates: out must hold float64")
-        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
-            raise ValueError("libcloudph++: cond_rates: unsupported strides")
-        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
-    if n_cell > 1 and strides[1] != 1:
-        raise ValueError("libcloudph++: cond_rates: out must have unit stride along cells")
-    if strides[0] < n_cell:
-        raise ValueError("libcloudph++: cond_rates: out's row stride is below n_cell")
-    return ptr, strides[0], isinstance(out, DeviceArray)
+    """(address, row stride in doubles, on_device) of an output array of cond_rates: (5 n_thr + 1, n_cell), see _rates_out"""
+    return _rates_out("cond_rates", out, len(COND_RATES) * n_thr + 1, n_cell)
 
 
 # ---- move rates per cell (include/lcx_move_rates.h)
@@ -427,51 +421,17 @@ MOVE_RATES_MAX_THR = 4                                               # LCX_MVR_M
 def move_rates_thresholds(r_thr):
     """the thresholds as lcx_move_rates_enable takes them, from a scalar or a sequence: 1 .. 4 finite, strictly increasing radii, the first
     may be 0 (every droplet)"""
-    r = [float(x) for x in np.atleast_1d(np.asarray(r_thr, dtype=np.float64)).ravel()]
-    if not 1 <= len(r) <= MOVE_RATES_MAX_THR:
-        raise ValueError("libcloudph++: move_rates: n_thr = %d is outside 1 .. %d" % (len(r), MOVE_RATES_MAX_THR))
-    if not all(x >= 0 and np.isfinite(x) for x in r):
-        raise ValueError("libcloudph++: move_rates: every threshold must be non-negative and finite")
-    if any(b <= a for a, b in zip(r, r[1:])):
-        raise ValueError("libcloudph++: move_rates: the thresholds must be strictly increasing")
-    return r
+    return _rates_thresholds("move_rates", r_thr, MOVE_RATES_MAX_THR, True)
 
 
 def move_rate_index(name, t=0, n_thr=MOVE_RATES_MAX_THR):
     """the row of a name of MOVE_RATES at threshold t, or of a row number, among 10 n_thr rows"""
-    n_rows = len(MOVE_RATES) * n_thr
-    if isinstance(name, str):
-        if name.lower() not in MOVE_RATES:
-            raise ValueError("libcloudph++: move_rates: unknown row %r (one of %s)" % (name, ", ".join(MOVE_RATES)))
-        t = int(t)
-        if not 0 <= t < n_thr:
-            raise ValueError("libcloudph++: move_rates: t = %d is outside 0 .. %d" % (t, n_thr - 1))
-        return len(MOVE_RATES) * t + MOVE_RATES.index(name.lower())
-    w = int(name)
-    if not 0 <= w < n_rows:
-        raise ValueError("libcloudph++: move_rates: row = %d is outside 0 .. %d" % (w, n_rows - 1))
-    return w
+    return _rate_index("move_rates", MOVE_RATES, name, t, n_thr)
 
 
 def move_rates_out(out, n_thr, n_cell):
-    """(address, row stride in doubles, on_device) of an output array of move_rates: (10 n_thr, n_cell) doubles with unit stride along
-    cells -- a writeable numpy array, or a DeviceArray for memory of the object's device"""
-    n_rows = len(MOVE_RATES) * n_thr
-    if len(out.shape) != 2 or out.shape[0] != n_rows or out.shape[1] != n_cell:
-        raise ValueError("libcloudph++: move_rates: out must be 2-D, (%d, n_cell)" % n_rows)
-    if isinstance(out, DeviceArray):
-        ptr, strides = out.ptr, out.strides
-    else:
-        if out.dtype != np.float64:
-            raise ValueError("libcloudph++: move_rates: out must hold float64")
-        if any(st % out.itemsize for st in out.strides) or not out.flags.writeable:
-            raise ValueError("libcloudph++: move_rates: unsupported strides")
-        ptr, strides = out.ctypes.data, [st // out.itemsize for st in out.strides]
-    if n_cell > 1 and strides[1] != 1:
-        raise ValueError("libcloudph++: move_rates: out must have unit stride along cells")
-    if strides[0] < n_cell:
-        raise ValueError("libcloudph++: move_rates: out's row stride is below n_cell")
-    return ptr, strides[0], isinstance(out, DeviceArray)
+    """(address, row stride in doubles, on_device) of an output array of move_rates: (10 n_thr, n_cell), see _rates_out"""
+    return _rates_out("move_rates", out, len(MOVE_RATES) * n_thr, n_cell)
 
 
 # ---- tracked super-droplets (include/lcx_track.h)
@@ -1019,6 +979,21 @@ class particles_t:
         self._chk(self._f("diag_batch")(self._h, arr, C.c_int(n_req), C.c_void_p(ptr), C.c_size_t(max(stride, 0)), C.c_int(int(on_device))))
         return out
 
+    # -- per-cell rate tables: what the three families below share
+    def _rates_info(self, fam, n_max):
+        """(enabled, the thresholds as a tuple, calls tallied since enable or the last reset) of the cond_rates or the move_rates"""
+        en, k, r, n = C.c_int(), C.c_int(), (C.c_double * n_max)(), C.c_ulonglong()
+        self._chk(self._f(fam + "_info")(self._h, C.byref(en), C.byref(k), r, C.byref(n)))
+        return bool(en.value), tuple(r[t] for t in range(k.value)), n.value
+
+    def _rates_read(self, fam, n_rows, reset, out):
+        """the table of family fam, (n_rows, n_cell) float64, into out or into a new numpy array; returns what it filled"""
+        n_cell = self.n_cell
+        arr = np.zeros((n_rows, n_cell), dtype=np.float64) if out is None else out
+        ptr, stride, on_device = _rates_out(fam, arr, n_rows, n_cell)
+        self._chk(self._f(fam + "_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        return arr
+
     # -- collision rates per cell (include/lcx_coal_rates.h; no reference counterpart)
     def coal_rates_enable(self, r_thr):
         """start (or restart from zero) the per-cell sums of what collisions move between cloud (r_wet < r_thr) and rain; before or
@@ -1037,10 +1012,7 @@ class particles_t:
     def coal_rates(self, reset=False, out=None):
         """the seven accumulators: a dict name (COAL_RATES) -> ndarray(n_cell) of float64; with out= (a (7, n_cell) float64 numpy array or
         DeviceArray of the object's device) fills and returns that.  reset: zero them behind the read."""
-        n_cell = self.n_cell
-        arr = np.zeros((len(COAL_RATES), n_cell), dtype=np.float64) if out is None else out
-        ptr, stride, on_device = coal_rates_out(arr, n_cell)
-        self._chk(self._f("coal_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        arr = self._rates_read("coal_rates", len(COAL_RATES), reset, out)
         return {nm: arr[w] for w, nm in enumerate(COAL_RATES)} if out is None else out
 
     def diag_coal_rate(self, name):
@@ -1059,18 +1031,13 @@ class particles_t:
 
     def cond_rates_info(self):
         """(enabled, the thresholds as a tuple, step_cond calls tallied since enable or the last reset)"""
-        en, k, r, n = C.c_int(), C.c_int(), (C.c_double * COND_RATES_MAX_THR)(), C.c_ulonglong()
-        self._chk(self._f("cond_rates_info")(self._h, C.byref(en), C.byref(k), r, C.byref(n)))
-        return bool(en.value), tuple(r[t] for t in range(k.value)), n.value
+        return self._rates_info("cond_rates", COND_RATES_MAX_THR)
 
     def cond_rates(self, reset=False, out=None):
         """the rows: a dict with "total_dm3" (n_cell,) and "above_dm3", "up_n", "up_m3", "down_n", "down_m3" (K, n_cell), float64; with out= (a
         (5 K + 1, n_cell) float64 numpy array or DeviceArray of the object's device) fills and returns that.  reset: zero them behind the read."""
-        n_cell, n_thr = self.n_cell, max(len(self.cond_rates_info()[1]), 1)
-        n_per = len(COND_RATES)
-        arr = np.zeros((n_per * n_thr + 1, n_cell), dtype=np.float64) if out is None else out
-        ptr, stride, on_device = cond_rates_out(arr, n_thr, n_cell)
-        self._chk(self._f("cond_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
+        n_per, n_thr = len(COND_RATES), max(len(self.cond_rates_info()[1]), 1)
+        arr = self._rates_read("cond_rates", n_per * n_thr + 1, reset, out)
         if out is not None:
             return out
         res = {nm: arr[w:n_per * n_thr:n_per] for w, nm in enumerate(COND_RATES)}
@@ -1094,21 +1061,14 @@ class particles_t:
 
     def move_rates_info(self):
         """(enabled, the thresholds as a tuple, moves tallied since enable or the last reset)"""
-        en, k, r, n = C.c_int(), C.c_int(), (C.c_double * MOVE_RATES_MAX_THR)(), C.c_ulonglong()
-        self._chk(self._f("move_rates_info")(self._h, C.byref(en), C.byref(k), r, C.byref(n)))
-        return bool(en.value), tuple(r[t] for t in range(k.value)), n.value
+        return self._rates_info("move_rates", MOVE_RATES_MAX_THR)
 
     def move_rates(self, reset=False, out=None):
         """the rows: a dict name of MOVE_RATES -> (K, n_cell) float64; with out= (a (10 K, n_cell) float64 numpy array or DeviceArray of the
         object's device) fills and returns that.  reset: zero them behind the read."""
-        n_cell, n_thr = self.n_cell, max(len(self.move_rates_info()[1]), 1)
-        n_per = len(MOVE_RATES)
-        arr = np.zeros((n_per * n_thr, n_cell), dtype=np.float64) if out is None else out
-        ptr, stride, on_device = move_rates_out(arr, n_thr, n_cell)
-        self._chk(self._f("move_rates_read")(self._h, C.c_void_p(ptr), C.c_size_t(stride), C.c_int(int(on_device)), C.c_int(int(bool(reset)))))
-        if out is not None:
-            return out
-        return {nm: arr[w::n_per] for w, nm in enumerate(MOVE_RATES)}
+        n_per, n_thr = len(MOVE_RATES), max(len(self.move_rates_info()[1]), 1)
+        arr = self._rates_read("move_rates", n_per * n_thr, reset, out)
+        return {nm: arr[w::n_per] for w, nm in enumerate(MOVE_RATES)} if out is None else out
 
     def diag_move_rate(self, name_or_row, t=0):
         """fills outbuf() with one row (a name of MOVE_RATES at threshold t, or a row number), normalised as a diag_*_mom result"""

@@ -531,6 +531,21 @@ def test_enable_again_with_other_thresholds_and_disable(real_t):
     rows, _, _ = tallied_step(prt, case, real_t, MV.bounds(four, real_t))
     assert as_block(prt).shape == (40, 16)
     assert_rows(as_block(prt), rows, "%s K = 4" % real_t.__name__)
+    # rows 32 .. 39 exist only at K = 4 (a mask of the count rows needs 64 bits for them): single rows, and the 40 rows into device memory
+    import torch
+    block = as_block(prt)
+    assert any((block[row] != 0).any() for row in (32, 38, 39)), "droplets above 60 um moved in this step: not zeros against zeros"
+    dv, rhod = prt.state_real("dv").astype(real_t), prt.state_real("rhod").astype(real_t)
+    for row in (31, 32, 38, 39):                                        # (even rows are counts, odd rows sums of m r^3)
+        prt.diag_move_rate(row)
+        out = np.frombuffer(prt.outbuf(), dtype=real_t).copy()
+        assert np.array_equal(out, (block[row].astype(real_t) / dv) / rhod), row
+    buf = torch.full((40, 24), -1., dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    prt.move_rates(out=lgrngn.DeviceArray(buf.data_ptr(), (40, 16), (24, 1)))
+    host = buf.cpu().numpy()
+    assert np.array_equal(host[:, :16], block)
+    assert (host[:, 16:] == -1).all(), "the elements between n_cell and the stride are not written"
     prt.move_rates_disable()
     assert prt.move_rates_info() == (False, (), 0)
     with pytest.raises(RuntimeError, match="not enabled"):
