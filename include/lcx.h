@@ -240,6 +240,12 @@ enum lcx_dbg2 {
                                         * the workgroup keeps no pair (the same bits) */
   LCX_DBG2_COAL_RANK_EXIT_ALWAYS = 1 << 2, /* tests: the form with the exit in every bound launch, also where the last launch's counters showed fewer than
                                         * 0.24 of the workgroups leaving ("raw_coal_exit": launches of the last lcx_step_async in that form) */
+  LCX_DBG2_NO_COAL_CELL_LIST = 1 << 4, /* the launch handed the tiles' flags is always k_coal_ranked<.., TILES>, as in round 10, never k_coal_cells (one wave per
+                                        * kept cell of the vote's list; the same bits), and the vote leaves no list.  "raw_coal_cells" = { launches of the last
+                                        * lcx_step_async in the list form, kept cells, cells with a pair } (the last two of that step's vote; 0 without a list) */
+  LCX_DBG2_COAL_CELL_LIST_ALWAYS = 1 << 5, /* tests: the list form in every launch that is handed the flags, the first one and a crowded vote included; the vote's counts
+                                        * then pause neither the bound nor the exit */
+  LCX_DBG2_COAL_CELL_LIST_SMALL = 1 << 6, /* tests: k_coal_cells on one workgroup, and cells above 64 droplets ranked by counting in memory */
   LCX_DBG2_NO_COAL_PREVOTE = 1 << 3    /* the form with the exit without the per-cell vote ahead of the launch (k_coal_umin, k_coal_cellvote): every workgroup
                                         * loads its cells' numbers, draws and votes for itself, as in round 9 (the same bits).  "raw_coal_prevote" = { launches
                                         * of the last lcx_step_async that were handed the tiles' flags, tiles flagged off, tiles, launches that fell back because

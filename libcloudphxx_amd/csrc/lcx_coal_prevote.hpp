@@ -54,6 +54,25 @@ LCX_HD T coal_cell_umin(const uint64_t off, const uint64_t end, const uint64_t c
   return m;
 }
 
+// The pairs of the cell [off, end) as k_coal_cells walks them: their number, and the position of pair j's first member (the same positions
+// coal_cell_umin draws at, so the vote and the kernel look at the same draws).
+LCX_HD uint64_t coal_cell_pairs(const uint64_t off, const uint64_t end) { return end > off ? (end - off) / 2 : 0; }
+LCX_HD uint64_t coal_pair_pos(const uint64_t off, const uint64_t j) { return off + 2 * j; }
+
+// The list of kept cells (k_coal_cellvote leaves it, k_coal_cells reads it) is shared out among the waves of a grid that does not grow with the
+// list: wave `wave` of workgroup `wg` takes the entries first, first + step, ... below the count.  Every entry below the count is taken by exactly
+// one wave whatever the grid (tools/coal_cells_check.cpp); the host sizes the grid with coal_cells_grid (at least one workgroup, at most `cap`).
+struct coal_list_share { uint64_t first, step; };
+LCX_HD coal_list_share coal_list_share_of(const uint64_t wg, const uint64_t n_wg, const uint64_t wave, const uint64_t waves_per_wg)
+{
+  return coal_list_share{wg * waves_per_wg + wave, n_wg * waves_per_wg};
+}
+LCX_HD uint64_t coal_cells_grid(const uint64_t n_cell, const uint64_t waves_per_wg, const uint64_t cap)
+{
+  const uint64_t want = (n_cell + waves_per_wg - 1) / waves_per_wg;
+  return want < 1 ? 1 : want > cap ? cap : want;
+}
+
 // Which tiles a kept cell must keep.  Tile k is the positions [k * tile, (k + 1) * tile) of the sorted order, one workgroup of k_coal_ranked
 // (tile = COAL_RANKED_POS).  The pair that starts at position p is examined by the lane that looks at p (p even) or at p - 1 (p odd); `tile` is
 // even, so p - 1 lies in p's tile, and every pair of the cell is examined in a tile that holds one of the cell's own positions: the tiles that

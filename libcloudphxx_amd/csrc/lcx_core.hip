@@ -439,7 +439,7 @@ struct Particles : IParticles {
   // for id loads one level later -- +0.17 ms on a launch of the 128^3 x 64 box in which none leaves, against -0.53 ms where all do, so the exit
   // breaks even at 0.17 / (0.17 + 0.53) = 0.24 of the workgroups leaving (EXPERIMENTS.md 7.10).  Below COAL_EXIT_MIN_PERCENT of them in a
   // launch's counters (or the sample of them) the next COAL_EXIT_PAUSE bound launches take round 8's form, then one probes again.  The same
-  // bits either way.
+  // bits either way.  (Which launch the flags are handed to, the tiles' or the kept cells': COAL_CELLS_MAX_PERCENT, with its figures, below.)
   static constexpr int COAL_EXIT_PAUSE = 32; static constexpr unsigned long long COAL_EXIT_MIN_PERCENT = 24;
   int exit_pause = 0;
   int last_coal_exit = 0;                    // ("raw_coal_exit": the coalescence launches of the last step_async in the EXIT form)
@@ -468,6 +468,45 @@ struct Particles : IParticles {
   uint64_t pv_call_of = 0, pv_seed_of = 0, pv_cells_of = 0; size_t pv_npart_of = 0;
   int pv_used = 0, pv_fallback = 0; size_t pv_tiles = 0; // ("raw_coal_prevote", of the last step_async)
   void join_umin() { if (umin_pending) { umin_pending = false; HIPCHK(hipStreamWaitEvent(st, ev_umin, 0)); } }
+  // ---- one wave per kept cell instead of the tiles (round 11; k_coal_cells, EXPERIMENTS.md 7.17) ----
+  // The vote also lists the kept cells and counts {cells with a pair, kept cells, pairs, pairs in kept cells, tiles flagged on}; the counts come back
+  // as the sample does (a pinned copy behind the launch, polled by the next step_async, never waited for).  The launch that is handed the flags is
+  // k_coal_cells where the last polled vote kept at most COAL_CELLS_MAX_PERCENT of the cells that hold a pair, else k_coal_ranked<.., TILES>; the
+  // first launch of an object and the first after a restore know no vote and take the tiles.  The same bits either way.
+  // COAL_CELLS_MAX_PERCENT, the break-even of the two launches (EXPERIMENTS.md 7.17; kernel trace, 64^3 x 64, f64, 32 768 tiles, us per launch):
+  //   box (steps 2-8)            cells kept   tiles flagged on   k_coal_cells   k_coal_ranked<.., TILES>
+  //   stratocumulus              0.1 %        1 %                13             38
+  //   sparse (--dt 0.05)         16-19 %      91-95 %            148-168        280-284
+  //   mixed (--dt 0.02)          50 %         52 %               412-425        197-202
+  //   coal-stress --dt 0.045     100 %        100 %              804-824        348-358
+  // The list form costs 10 us + 3.1 ns per kept cell; the tiles cost 1.07 ns per tile (the walk over the flags: 35 us here, 0.22 ms at 128^3) +
+  // 9.6 ns per tile flagged on.  How many tiles a kept cell flags depends on how the kept cells lie: scattered (sparse) each flags a tile of its
+  // own and the list form wins at 19 % and beyond; side by side (mixed: eight kept cells per kept tile) the lines cross at
+  // 10 + 800 x = 38 + 330 x, x = 6 % of the cells.  The threshold is the lower of the two, so that no layout pays.
+  static constexpr unsigned long long COAL_CELLS_MAX_PERCENT = 6;
+  DevBuf<uint32_t> coal_kept_cells; DevBuf<unsigned long long> coal_vote_cnt; void *cells_pinned = nullptr; hipEvent_t ev_cells = nullptr;
+  bool cells_vote_pending = false, cells_vote_of_list = false, cells_vote_known = false, cells_listed = false;
+  unsigned long long cells_kept = 0, cells_with_pair = 0, cells_tiles_sent = 0;
+  int last_coal_cells = 0;                   // ("raw_coal_cells": the coalescence launches of the last step_async in the list form)
+  void poll_cells_vote()
+  {
+    if (!cells_vote_pending || hipEventQuery(ev_cells) != hipSuccess) return;
+    cells_vote_pending = false;
+    const unsigned long long *h = static_cast<const unsigned long long *>(cells_pinned);
+    const coal_vote_sums v = coal_vote_sums_of(h);
+    cells_vote_known = true; cells_with_pair = v.with_pair; cells_kept = v.kept;
+    if (!cells_vote_of_list) return;         // (a launch of the tiles has fed the sample itself)
+    if (dbg2(LCX_DBG2_COAL_CELL_LIST_ALWAYS)) return;       // (tests: a forced launch stays forced -- counted per cell, a box that keeps every cell skips no pair)
+    // the list form feeds the two pause rules from the vote's exact counts: pairs of cells voted off count as skipped, all pairs as examined,
+    // tiles flagged off as left, tiles as launched
+    const unsigned long long examined = v.pairs, skipped = v.pairs - v.pairs_kept, launched = cells_tiles_sent, left = launched - v.tiles_on;
+    if (examined && skipped * COAL_SKIP_MIN_SHARE < examined) skip_pause = COAL_SKIP_PAUSE;
+    if (launched && left * 100 < launched * COAL_EXIT_MIN_PERCENT) exit_pause = COAL_EXIT_PAUSE;
+  }
+  bool cells_list_wanted() const
+  {
+    return dbg2(LCX_DBG2_COAL_CELL_LIST_ALWAYS) || (cells_vote_known && cells_kept * 100 <= cells_with_pair * COAL_CELLS_MAX_PERCENT);
+  }
   bool coal_bound_armed = false;             // step_async's own hskpng_vterm has just left the maxima: the FIRST coalescence substep may use them
   int last_coal_skip = 0;                    // ("raw_coal_skip": the coalescence launches of the last step_async that used a bound)
   unsigned long long coal_bound_unused = 0;  // ("raw_coal_bound_unused": step_asyncs of this object whose velocity pass collected maxima that no launch used --
@@ -600,6 +639,8 @@ struct Particles : IParticles {
     if (diag_stage) (void)hipHostFree(diag_stage);
     if (skip_pinned) (void)hipHostFree(skip_pinned);
     if (ev_skip) (void)hipEventDestroy(ev_skip);
+    if (cells_pinned) (void)hipHostFree(cells_pinned);
+    if (ev_cells) (void)hipEventDestroy(ev_cells);
     // (the copy stream reads the staging areas: it is drained before they are freed)
     if (st_copy) { (void)hipStreamSynchronize(st_copy); (void)hipStreamDestroy(st_copy); }
     for (HostStage *h : {&hstage_in, &hstage_out}) if (h->p) (void)hipHostFree(h->p);
@@ -2203,10 +2244,11 @@ struct Particles : IParticles {
       dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));              // (a workgroup per tile; with the tiles' flags: per COAL_TILES_PER_WG tiles)
       last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
       coal_skip_args<T> ska{};
-      bool exits = false;
+      bool exits = false, by_cells = false;           // (by_cells: k_coal_cells over the vote's list in place of the tiles' launch)
+      cells_listed = false;
       if (bound_armed && !n_max_stale) {
         const bool counted = dbg2(LCX_DBG2_COAL_SKIP_COUNT);
-        if (!counted) { coal_skip_sample.alloc(128); HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 128 * sizeof(unsigned long long), st)); }
+        if (!counted) coal_skip_sample.alloc(128);
         exits = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
         if (!exits && exit_pause > 0) --exit_pause;
         if (exits) ++last_coal_exit;
@@ -2218,13 +2260,22 @@ struct Particles : IParticles {
           if (pv_call_of == rs.call && pv_seed_of == rs.seed && pv_cells_of == cells_version && pv_npart_of == npart) {
             coal_tile_flag.alloc(gr.x);
             HIPCHK(hipMemsetAsync(coal_tile_flag.p, 0, size_t(gr.x) * sizeof(uint32_t), st));
+            coal_vote_out vo{nullptr, nullptr};
+            if (!dbg2(LCX_DBG2_NO_COAL_CELL_LIST)) {                 // (the vote also lists the kept cells and counts what the host chooses the form by)
+              coal_kept_cells.alloc(ncell); coal_vote_cnt.alloc(CV_WORDS);
+              HIPCHK(hipMemsetAsync(coal_vote_cnt.p, 0, CV_WORDS * sizeof(unsigned long long), st));
+              vo = coal_vote_out{coal_kept_cells.p, coal_vote_cnt.p};
+            }
+            cells_listed = vo.list != nullptr;
             hipLaunchKernelGGL(k_coal_cellvote<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const uint32_t *)cell_start.p, (const uint32_t *)coal_cmax.p, (const T *)dv.p,
-                               (const T *)coal_umin.p, (const n_t *)coal_n_max.p, (const T *)coal_emax.p, n_emax, T(kernel_r_max), T(dt_sub), coal_tile_flag.p, uint64_t(gr.x));
+                               (const T *)coal_umin.p, (const n_t *)coal_n_max.p, (const T *)coal_emax.p, n_emax, T(kernel_r_max), T(dt_sub), coal_tile_flag.p, uint64_t(gr.x), vo);
             flags = coal_tile_flag.p; pv_tiles = gr.x; ++pv_used;
+            by_cells = cells_listed && !counted && cells_list_wanted();
           }
           else ++pv_fallback;     // (defensive: no path reaches it today -- step_async asks for a bound only where coal() neither re-sorts nor draws
                                   // anything but the salts counted above, and no test takes it; it keeps a later change to either from using stale draws)
         }
+        if (!counted && !by_cells) HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 128 * sizeof(unsigned long long), st));       // (the list form feeds no sample)
         ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p,
                                 counted && exits ? coal_skip_cnt.p + 2 : nullptr, flags, counted && flags ? coal_pv_disagree.p : nullptr};
         if (flags) gr.x = (gr.x + COAL_TILES_PER_WG - 1) / COAL_TILES_PER_WG;
@@ -2241,13 +2292,30 @@ struct Particles : IParticles {
           hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
                              deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
         };
-        if (ska.cmax && exits && ska.flags) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL, true>); else launch(k_coal_ranked<T, false, true, true, TL, true>); }
+        if (by_cells) {
+          const coal_cells_args ca{coal_kept_cells.p, coal_vote_cnt.p + CV_KEPT, coal_cmax.p, coal_n_max.p, n_emax,
+                                   dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? uint32_t(WAVE) : uint32_t(CELLRANK_MAX)};
+          const dim3 gc(unsigned(coal_cells_grid(ncell, COAL_CELLS_WAVES, dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? 1 : COAL_CELLS_GRID_CAP)));
+          auto launch_cells = [&](auto kern) {
+            hipLaunchKernelGGL(kern, gc, dim3(BS), 0, st, ca, (const T *)coal_emax.p, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)cell_start.p, deferred_rs,
+                               A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ta);
+          };
+          if (coal_marks_dead) launch_cells(k_coal_cells<T, true, TL>); else launch_cells(k_coal_cells<T, false, TL>);
+        }
+        else if (ska.cmax && exits && ska.flags) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL, true>); else launch(k_coal_ranked<T, false, true, true, TL, true>); }
         else if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL>); else launch(k_coal_ranked<T, false, true, true, TL>); }
         else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, false, TL>); else launch(k_coal_ranked<T, false, true, false, TL>); }
         else if (coal_marks_dead) launch(k_coal_ranked<T, true, false, false, TL>); else launch(k_coal_ranked<T, false, false, false, TL>);
       };
       if (cr.on) launch_all(std::true_type{}); else launch_all(std::false_type{});
-      if (ska.cmax && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
+      if (by_cells) ++last_coal_cells;
+      if (cells_listed && !cells_vote_pending) {       // (the vote's counts on their way to the host: poll_cells_vote)
+        if (!cells_pinned) { HIPCHK(hipHostMalloc(&cells_pinned, CV_WORDS * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_cells, hipEventDisableTiming)); }
+        HIPCHK(hipMemcpyAsync(cells_pinned, coal_vote_cnt.p, CV_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(ev_cells, st));
+        cells_vote_pending = true; cells_vote_of_list = by_cells; cells_tiles_sent = pv_tiles;
+      }
+      if (ska.cmax && !by_cells && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
         if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 128 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
         skip_sample_n = ska.cnt ? 4 : 128;
         HIPCHK(hipMemcpyAsync(skip_pinned, ska.cnt ? ska.cnt : ska.sample, skip_sample_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -3138,7 +3206,7 @@ struct Particles : IParticles {
     const bool rlx_now = opts.rlx && rlx_fires();
     const bool rlx_plain = rlx_now && (distmem() || nphys == 0 || nphys + rlx_max_new > cap);
     rng_recs.clear();
-    last_coal_ranked = 0; last_coal_skip = 0; last_coal_exit = 0; coal_bound_armed = false;
+    last_coal_ranked = 0; last_coal_skip = 0; last_coal_exit = 0; last_coal_cells = 0; cells_listed = false; coal_bound_armed = false;
     if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) { coal_skip_cnt.alloc_zero(4, st); coal_pv_disagree.alloc_zero(1, st); }
     coal_wg_no_exit = 0;
     vt_fix_pending = false;                           // (a flag of one step_async: nothing of an earlier call is pending)
@@ -3148,7 +3216,7 @@ struct Particles : IParticles {
     hskpng_Tpr(opts.sedi || opts.coal || opts.cond);
     // (the velocity pass leaves the per-cell maxima of coal_pair's bound where the first coalescence substep, right behind it, will rank for itself:
     // nothing in between writes rw2, vt, n or the cells)
-    poll_skip_sample();
+    poll_skip_sample(); poll_cells_vote();
     const bool paused = opts.coal && skip_pause > 0;
     if (paused) --skip_pause;
     const bool want_bound = opts.coal && !paused && coal_skip_wanted();
@@ -3428,6 +3496,10 @@ struct Particles : IParticles {
       if (pv_used && pv_tiles) { auto h = d2h(coal_tile_flag.p, pv_tiles); for (auto x : h) off += x == 0u; }
       v = {(unsigned long long)pv_used, off, (unsigned long long)pv_tiles, (unsigned long long)pv_fallback};
       if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) v.push_back(coal_pv_disagree.p ? d2h(coal_pv_disagree.p, 1)[0] : 0ull);
+    }
+    else if (s == "raw_coal_cells") {              // of the last step_async: launches in the list form (k_coal_cells), kept cells, cells with a pair (its vote's; 0 without a list)
+      v.assign(3, 0ull); v[0] = (unsigned long long)last_coal_cells;
+      if (cells_listed) { auto h = d2h(coal_vote_cnt.p, CV_WORDS); const coal_vote_sums cv = coal_vote_sums_of(h.data()); v[1] = cv.kept; v[2] = cv.with_pair; }
     }
     else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
@@ -4255,6 +4327,7 @@ struct Particles : IParticles {
       deferred_rs.un = nullptr; last_shuffle_rs.un = nullptr;
       should_now_run_async = should_now_run_cond = selected_before_counting = false;
       skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false; umin_made = false; pv_used = 0; pv_fallback = 0; pv_tiles = 0;
+      cells_vote_pending = cells_vote_known = cells_listed = false; cells_kept = cells_with_pair = 0; last_coal_cells = 0;
       sync();
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)

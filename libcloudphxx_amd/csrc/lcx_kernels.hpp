@@ -3004,20 +3004,178 @@ k_coal_umin(size_t n_cell, const uint32_t *cell_start, uint64_t call, uint64_t s
 // `lane's bound < 1 && u >= lane's bound` for every pair of the cell -- a tile is only flagged off where every lane would have skipped.  A flagged tile
 // is decided again by its own lanes, so the margin costs nothing.  A NaN bound (a poisoned cell, an infinite maximum, a cell within 11 um of the
 // table's end) fails the comparison and keeps the cell.  A cell without a pair keeps nothing.
+// Round 11: THE VOTE ALSO LEAVES A LIST (vo.list != nullptr): every kept cell's index is appended to vo.list (room for n_cell), in the order the waves'
+// atomics arrive -- nobody may rely on it, a cell's pairs touch that cell's droplets alone -- and vo.cnt counts what the host decides from
+// (lcx_core.hip poll_cells_vote): kept cells (the list's length, word CV_KEPT), and cells with a pair, pairs, pairs in kept cells and tiles flagged
+// on.  One atomic per wave and counter that the wave adds to.  Every wave with a pair adds to the middle two, and 33 000 waves adding to one word
+// took 0.1 ms at 64^3 cells (12 ns an atomic, one behind the other in the L2; EXPERIMENTS.md 7.17): those four are kept in CV_SLOTS copies, a
+// cache line each, a wave adding to the copy of its number, and the host adds the copies up (coal_vote_sums).  The flags are then set by an
+// exchange so that a tile is counted by the first cell to flag it.
+struct coal_vote_out { uint32_t *list; unsigned long long *cnt; };
+constexpr int CV_KEPT = 0, CV_SLOTS = 64, CV_SLOT_WORDS = 16, CV_SLOT0 = 16, CV_WORDS = CV_SLOT0 + CV_SLOTS * CV_SLOT_WORDS;
+constexpr int CVS_WITH_PAIR = 0, CVS_PAIRS = 1, CVS_PAIRS_KEPT = 2, CVS_TILES_ON = 3;
+struct coal_vote_sums { unsigned long long kept, with_pair, pairs, pairs_kept, tiles_on; };
+inline coal_vote_sums coal_vote_sums_of(const unsigned long long *h)
+{
+  coal_vote_sums v{h[CV_KEPT], 0, 0, 0, 0};
+  for (int i = 0; i < CV_SLOTS; ++i) {
+    const unsigned long long *w = h + CV_SLOT0 + i * CV_SLOT_WORDS;
+    v.with_pair += w[CVS_WITH_PAIR]; v.pairs += w[CVS_PAIRS]; v.pairs_kept += w[CVS_PAIRS_KEPT]; v.tiles_on += w[CVS_TILES_ON];
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d);
+  return v;
+}
 template <class T>
 __global__ void __launch_bounds__(BS)
 k_coal_cellvote(size_t n_cell, const uint32_t *cell_start, const uint32_t *cmax, const T *dv, const T *umin, const n_t *n_max, const T *emax, int n_emax,
-                T r_max, T dt, uint32_t *flags, uint64_t n_tiles)
+                T r_max, T dt, uint32_t *flags, uint64_t n_tiles, coal_vote_out vo = coal_vote_out{nullptr, nullptr})
 {
-  const size_t c = gid(); if (c >= n_cell) return;
-  const uint32_t off = cell_start[c], end = cell_start[c + 1];
-  if (end - off < 2u) return;
-  struct alignas(8) pairU { uint32_t a, b; };
-  const pairU m = *reinterpret_cast<const pairU *>(cmax + 2 * c);
-  const T bound = coal_bound<T>(m.a, m.b, dv[c], coal_scale_of<T>(n_t(end - off)), dt, T(*n_max), r_max, emax, n_emax) * T(1 + 1. / 1024);
-  if (bound < T(1) && umin[c] >= bound) return;
-  const coal_tile_range r = coal_cell_tiles(off, end, COAL_RANKED_POS);
-  for (uint64_t k = r.first; k <= r.last && k < n_tiles; ++k) flags[k] = 1u;                 // (every position lies below n_part: k < n_tiles holds)
+  const size_t c = gid();
+  uint32_t off = 0, end = 0;
+  if (c < n_cell) { off = cell_start[c]; end = cell_start[c + 1]; }
+  const bool has_pair = end - off >= 2u && end > off;
+  bool kept = false;
+  if (has_pair) {
+    struct alignas(8) pairU { uint32_t a, b; };
+    const pairU m = *reinterpret_cast<const pairU *>(cmax + 2 * c);
+    const T bound = coal_bound<T>(m.a, m.b, dv[c], coal_scale_of<T>(n_t(end - off)), dt, T(*n_max), r_max, emax, n_emax) * T(1 + 1. / 1024);
+    kept = !(bound < T(1) && umin[c] >= bound);
+  }
+  unsigned long long tiles_on = 0;
+  if (kept) {
+    const coal_tile_range r = coal_cell_tiles(off, end, COAL_RANKED_POS);
+    for (uint64_t k = r.first; k <= r.last && k < n_tiles; ++k) {                              // (every position lies below n_part: k < n_tiles holds)
+      if (vo.list) tiles_on += atomicExch(&flags[k], 1u) == 0u; else flags[k] = 1u;
+    }
+  }
+  if (!vo.list) return;
+  const unsigned long long with_pair = __ballot(has_pair), keeps = __ballot(kept);
+  if (!with_pair) return;                                                                      // (uniform)
+  const unsigned long long pairs_here = has_pair ? coal_cell_pairs(off, end) : 0;
+  const unsigned long long pairs = wave_sum(pairs_here), pairs_kept = wave_sum(kept ? pairs_here : 0), on = wave_sum(tiles_on);
+  unsigned long long base = 0;
+  if (lane_id() == 0) {
+    unsigned long long *slot = vo.cnt + CV_SLOT0 + ((blockIdx.x * (BS / WAVE) + wave_id()) % CV_SLOTS) * CV_SLOT_WORDS;
+    atomicAdd(slot + CVS_WITH_PAIR, (unsigned long long)__popcll(with_pair));
+    atomicAdd(slot + CVS_PAIRS, pairs);
+    if (keeps) {
+      base = atomicAdd(vo.cnt + CV_KEPT, (unsigned long long)__popcll(keeps));
+      atomicAdd(slot + CVS_PAIRS_KEPT, pairs_kept);
+      if (on) atomicAdd(slot + CVS_TILES_ON, on);
+    }
+  }
+  base = __shfl(base, 0);
+  if (kept) vo.list[base + __popcll(keeps & ((1ull << lane_id()) - 1ull))] = uint32_t(c);      // (base + the wave's kept cells <= cells with a pair <= n_cell)
+}
+// k_coal_cells: ONE WAVE PER LISTED CELL (round 11; EXPERIMENTS.md 7.17).  A kept tile of k_coal_ranked<.., TILES> costs a workgroup -- ids of 1 024
+// positions, keys, LDS atomics, a scan, five barriers -- to find the order of about eight cells of which usually one holds one kept pair.  Here
+// the waves of a grid that does not grow with the box stride over the vote's list (coal_list_share_of) up to its count, read once per wave.  A
+// wave owns its cell [off, end) alone: no workgroup barrier, no wave waits for another, every loop is bounded by the count or the cell's size.
+//   1. the lanes test the cell's pairs as a lane of the tile kernel does -- pair j at position off + 2 j, u = philox::u01<T>(p, call, seed),
+//      coal_bound of the same cmax, dv, scale, n_max and emax -- before any id is loaded; a cell in which no pair is kept after all (the vote
+//      errs toward keeping) is left there;
+//   2. the cell's ids are loaded from the arrival-ordered `in` (four per lane cover CELLRANK_MAX), the keys shuffle_un(id, s1, s2) are staged
+//      in the wave's own slice of LDS and every key is ranked by counting the cell's smaller keys (broadcast reads, four keys per read); the ids
+//      go to the wave's slice by rank.  The keys are unique: this is the order that every other ranking gives;
+//   3. a lane that kept pair j runs coal_collide with the ids at ranks 2 j and 2 j + 1, pre = true, its u and the cell's dv: the tile kernel's
+//      call, hence the same bits.
+// A cell above `lds_cap` droplets (the host launches the ranked path only where none is above CELLRANK_MAX; LCX_DBG2_COAL_CELL_LIST_SMALL
+// lowers the cap for the tests) is ranked window by window of CELLRANK_MAX ranks, counting in memory: correct for any size, slow.
+constexpr int COAL_CELLS_WAVES = BS / WAVE;
+constexpr uint64_t COAL_CELLS_GRID_CAP = 2048;      // workgroups at most: eight per CU of a 256-CU device at 8 KiB of LDS each
+struct coal_cells_args {
+  const uint32_t *list; const unsigned long long *count;       // the vote's list and its length (vo.cnt + CV_KEPT)
+  const uint32_t *cmax; const n_t *n_max; int n_emax; uint32_t lds_cap;
+};
+template <class T, bool MARK, bool TALLY>
+__global__ void __launch_bounds__(BS)
+k_coal_cells(coal_cells_args ca, const T *emax, const uint32_t *in, const uint32_t *cell_start, rng_src r,
+             n_t *n, T *rw2, T *vt, T *rd3, const T *dv, T dt, coal_kernel_cfg<T> kc, u01_src<T> rs, uint32_t *ijk_mark, coal_tally_arg<T, TALLY> ta = {})
+{
+  constexpr uint32_t W = CELLRANK_MAX, PER = W / WAVE;           // ranks per window, entries per lane
+  static_assert(PER == 4, "the keys are read four at a time");
+  __shared__ alignas(16) uint32_t keys_s[COAL_CELLS_WAVES][W];
+  __shared__ uint32_t ids_s[COAL_CELLS_WAVES][W];
+  kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
+  if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
+  auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+  const uint32_t lane = lane_id();
+  uint32_t *keys = keys_s[wave_id()], *ids = ids_s[wave_id()];
+  const uint64_t count = *ca.count;
+  const T n_max = T(*ca.n_max);
+  const coal_list_share sh = coal_list_share_of(blockIdx.x, gridDim.x, wave_id(), COAL_CELLS_WAVES);
+  for (uint64_t li = sh.first; li < count; li += sh.step) {
+    const uint32_t c = ca.list[li];
+    const uint32_t off = cell_start[c], end = cell_start[c + 1];
+    const uint32_t n_pairs = uint32_t(coal_cell_pairs(off, end));
+    if (n_pairs == 0) continue;
+    const uint32_t m = end - off;
+    struct alignas(8) pairU { uint32_t a, b; };
+    const pairU mx2 = *reinterpret_cast<const pairU *>(ca.cmax + 2 * size_t(c));
+    const T dvc = dv[c], scl = coal_scale_of<T>(n_t(m));
+    const T bound = coal_bound<T>(mx2.a, mx2.b, dvc, scl, dt, n_max, kc.r_max, emax, ca.n_emax);
+    for (uint32_t base = 0; base < 2 * n_pairs; base += W) {          // (one window wherever the cell has at most CELLRANK_MAX droplets)
+      // 1. the window's pairs, two per lane at most (the loops over the two are kept rolled: one copy of the draw and one of coal_collide)
+      T u0 = T(0), u1 = T(0); bool kept0 = false, kept1 = false;
+#pragma unroll 1
+      for (uint32_t k = 0; k < 2; ++k) {
+        const uint32_t j = base / 2 + lane + k * WAVE;
+        T uu = T(0); bool kk = false;
+        if (j < n_pairs) {
+          uu = philox::u01<T>(coal_pair_pos(off, j), rs.call, rs.seed);
+          kk = !(bound < T(1) && uu >= bound);
+        }
+        if (k) { u1 = uu; kept1 = kk; } else { u0 = uu; kept0 = kk; }
+        if (base / 2 + WAVE >= n_pairs) break;                          // (uniform: the window holds no second pair for any lane)
+      }
+      if (!__any(kept0 || kept1)) continue;                       // (uniform)
+      // 2. the ranked ids of the window's ranks [base, base + W)
+      wave_sync();                                                    // (the lanes of the window before may still be reading ids)
+      if (m <= ca.lds_cap && m <= W) {
+        const uint32_t nk = (m + WAVE - 1) / WAVE;                    // (uniform)
+        uint32_t id[PER], key[PER], rank[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+          const uint32_t q = lane + k * WAVE;
+          id[k] = 0u; key[k] = 0xFFFFFFFFu; rank[k] = 0u;
+          if (k < nk) { if (q < m) { id[k] = in[off + q]; key[k] = shuffle_un(id[k], r.s1, r.s2); } }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) if (k < nk) keys[lane + k * WAVE] = lane + k * WAVE < m ? key[k] : 0xFFFFFFFFu;    // (padding: smaller than no key)
+        wave_sync();
+        for (uint32_t q = 0; q < nk * WAVE; q += 4) {
+          const uint4 o = *reinterpret_cast<const uint4 *>(keys + q);
+#pragma unroll
+          for (uint32_t k = 0; k < PER; ++k) if (k < nk) rank[k] += uint32_t(o.x < key[k]) + uint32_t(o.y < key[k]) + uint32_t(o.z < key[k]) + uint32_t(o.w < key[k]);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) if (k < nk && lane + k * WAVE < m) ids[rank[k]] = id[k];                             // (unique keys: rank < m <= W)
+      } else {
+        for (uint32_t q = lane; q < m; q += WAVE) {
+          const uint32_t idq = in[off + q], mine = shuffle_un(idq, r.s1, r.s2);
+          uint32_t rank = 0;
+          for (uint32_t j = 0; j < m; ++j) rank += shuffle_un(in[off + j], r.s1, r.s2) < mine;
+          if (rank - base < W) ids[rank - base] = idq;                // (unsigned: ranks below the window wrap above it)
+        }
+      }
+      wave_sync();
+      // 3. the kept pairs
+#pragma unroll 1
+      for (uint32_t k = 0; k < 2; ++k) {
+        if (!(k ? kept1 : kept0)) continue;
+        const uint32_t j = base / 2 + lane + k * WAVE, jw = lane + k * WAVE;
+        coal_own own;
+        own.p = size_t(coal_pair_pos(off, j)); own.ca = c; own.off = off; own.end = end; own.second = false; own.shift = false;
+        coal_collide<T, false, TALLY>(own, ids[2 * jw], ids[2 * jw + 1], scl, true, k ? u1 : u0, dvc, n, rw2, vt, rd3, (T *)nullptr, dv, dt, kc, rs, 0, (int *)nullptr,
+                                      (T *)nullptr, (T *)nullptr, ijk_mark, ta);
+      }
+    }
+  }
 }
 // weighted_summator, coal.ipp:57-97,458-480 (only with more than one kappa in the run)
 template <class T>

@@ -132,6 +132,9 @@ class dbg2(enum.IntFlag):
     NO_COAL_RANK_EXIT = 1 << 1
     COAL_RANK_EXIT_ALWAYS = 1 << 2
     NO_COAL_PREVOTE = 1 << 3
+    NO_COAL_CELL_LIST = 1 << 4
+    COAL_CELL_LIST_ALWAYS = 1 << 5
+    COAL_CELL_LIST_SMALL = 1 << 6
 
 
 class cond_kernel(enum.IntEnum):
