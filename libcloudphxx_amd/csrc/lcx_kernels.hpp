@@ -1345,13 +1345,13 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
 // Fast arithmetic's production kernel since round 3: the growth rate of k_cond_fast under the lean bracketed secant of lcx_math.hpp
 // (advance_rw2_lean_with) instead of TOMS748 -- no iteration budget, no second launch, no fold: the iteration counts are short and even.
-// Round 4.  The solver's bookkeeping pared down (lcx_math.hpp, lean2_*: the same operations on the droplet's numbers, straight-line
-// loop body) and the growth rate's helper functions without the instructions that are identities here (OPT bit 2): 776 -> 671 vector
-// instructions per wave in the spin-up steps that rounds 1-3 profiled (637 in the settled box), the same rw2 bit for bit (SOLVER = 1 keeps
-// round 3's form for the test that shows it); the launch 3.43 -> 3.0 ms.  At that point the kernel is no longer bound by its vector
-// ALU alone: 0.83 busy, and 10.4 GB of traffic (its own 56 B per droplet + the carried scatter's 20) in 2.9 ms is 3.6 of the 4.85 TB/s
-// that a copy reaches on the same box.  UNI: a run with ONE hygroscopicity (one dry distribution, no user-set particles) passes it as
-// a scalar -- 8 B per droplet that the kernel does not read.
+// Round 4.  The solver's bookkeeping pared down (lcx_math.hpp, lean2_*: the same operations on the droplet's numbers, straight-line loop
+// body) and the growth rate's helper functions without the instructions that are identities here (OPT bit 2): 776 -> 671 vector
+// instructions per wave in the spin-up steps that rounds 1-3 profiled (637 in the settled box), the same rw2 bit for bit in double (SOLVER
+// = 1 keeps round 3's form for the test that shows it; in float it also keeps round 3's stopping rule, which lean2_loop has left); 3.43 ->
+// 3.0 ms.  At that point the kernel is no longer bound by its vector ALU alone: 0.83 busy, and 10.4 GB of traffic (its own 56 B per droplet
+// + the carried scatter's 20) in 2.9 ms is 3.6 of the 4.85 TB/s that a copy reaches on the same box.  UNI: a run with ONE hygroscopicity
+// (one dry distribution, no user-set particles) passes it as a scalar -- 8 B per droplet that the kernel does not read.
 // Measured and dropped on the way (profiles/r04_*):
 //  * Dealing a workgroup's droplets to its waves by the iteration count each needed in the previous step (a byte per storage slot, one
 //    ballot, two barriers), so that the slow ones share a wave: the count does not repeat well enough -- 96 % of the droplets that needed at
@@ -1360,7 +1360,7 @@ __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 //  * Two passes: every droplet's loop stopped after ONE evaluation, the 9 % that have not converged listed with the loop's state
 //    (seven reals, one atomic per wave) and taken up where they stand by a dense second launch -- the same bits; the first pass 637 -> 590
 //    instructions per wave and not a microsecond faster (2.98 against 3.00 ms: the memory side), the second pass 0.75 ms of gathers.
-// SOLVER: 0 the lean solver in round 4's form, 1 in round 3's (the same bits, kept for the test that shows it), 2 TOMS748 -- the
+// SOLVER: 0 the lean solver in round 4's form, 1 in round 3's (the same bits in double, kept for the test that shows it), 2 TOMS748 -- the
 // reference's iterates on this kernel's growth-rate arithmetic (opts_init.cond_solver = 1), in the same storage-order walk
 // Round 5 (late): droplets whose bracket may hold SEVERAL roots (lcx_math.hpp lean2_head, `suspicious`) are not solved here: they
 // are listed (one atomic per wave that has any: about 0.1 % of the droplets of bench.py's settled boxes, a tenth of a box whose aerosol is just

@@ -248,7 +248,10 @@ def lgrngn_bimodal():
 
 
 def box_fields(oi, seed=0, supersat=True):
-    """th, rv, rhod, Cx, Cy, Cz for a box: smooth, non-uniform, RH ~ 0.95..1.01; |C| <= 0.3"""
+    """th, rv, rhod, Cx, Cy, Cz for a box: smooth, non-uniform, |C| <= 0.3.  Supersaturated throughout: the object's own RH reads
+    1.23 .. 1.64 on box_opts(4, 4, 6, 64), with supersat=True and with False (th 289 K at rhod 1.1 is T = 278 K, where 8 g/kg is 1.2
+    times saturation).  The fields stay as they are -- every measured bar of the parity tests rests on them; a box with RH < 1 (0.80 ..
+    1.03 by level, crafted from the target RH) is tests/test_oracle_cond.py crafted_fields."""
     nx, ny, nz = max(oi.nx, 1), max(oi.ny, 1), max(oi.nz, 1)
     shp = tuple(n for n, f in zip((oi.nx, oi.ny, oi.nz), (1, 1, 1)) if n > 0)
     rng = np.random.default_rng(seed)
