@@ -395,7 +395,9 @@ int lcx_get_state_u64(lcx_particles *, const char *name, unsigned long long *out
  * 1 the one with the Onishi kernel, 2 the production variant (tabulated efficiencies, the library's own random numbers, fused step).
  * "raw_coal_ranked" (u64, one value): how many coalescence launches of the last lcx_step_async ranked their cells' shuffled order for
  * themselves (k_coal_ranked: the first substep at most); 0: each read an order that a ranking kernel had written to memory (reading
- * "raw_sorted_id" ahead of the step, crowded cells or LCX_DBG_NO_RANK_IN_COAL make it so). */
+ * "raw_sorted_id" ahead of the step, crowded cells or LCX_DBG_NO_RANK_IN_COAL make it so).  "raw_move_kernel" (u64, one value): the k_move
+ * instantiation of the last move launch (a step_async, or one of the stages "adve" / "sedi" / "bcnd") -- bits 0-3 SPEC (1 three-dimensional,
+ * 2 the full step's pass, 4 a slab with neighbours, 8 implicit), bit 4 PC (predictor-corrector), bit 5 TURB (SGS velocities); 0 before any. */
 int lcx_get_state_real(lcx_particles *, const char *name, double *out, size_t cap, size_t *n);
 /* overwrite particle state (all arrays of length n; x/y/z may be NULL for absent dimensions);
  * lets a test start the device from an oracle state */

@@ -2390,6 +2390,7 @@ struct Particles : IParticles {
     a.check_n = !coal_marks_dead || zero_n_unmarked;
     if (reindex) zero_n_unmarked = false;
     const bool pc = adve_scheme == LCX_ADVE_PRED_CORR, tb = a.up != nullptr;
+    last_move_kernel = (pc ? 16 : 0) | (tb ? 32 : 0);              // ("raw_move_kernel": PC, TURB; SPEC is added where one is chosen)
     if (pc && tb) hipLaunchKernelGGL((k_move<T, true, true>), dim3(blocks), dim3(BS), 0, st, a);
     else if (pc) hipLaunchKernelGGL((k_move<T, true, false>), dim3(blocks), dim3(BS), 0, st, a);
     else if (tb) hipLaunchKernelGGL((k_move<T, false, true>), dim3(blocks), dim3(BS), 0, st, a);
@@ -2397,6 +2398,7 @@ struct Particles : IParticles {
       const bool full = do_adve && do_sedi && !do_subs && do_bcnd && reindex && halo == 0 && !o.open_side_walls && !o.periodic_topbot_walls &&
                         (adve_scheme == LCX_ADVE_EULER || adve_scheme == LCX_ADVE_IMPLICIT);
       const int spec = !full ? MOVE_3D : MOVE_3D | MOVE_FULL | (a.distmem ? MOVE_DISTMEM : 0) | (adve_scheme == LCX_ADVE_IMPLICIT ? MOVE_IMPLICIT : 0);
+      last_move_kernel |= spec;
       switch (spec) {
         case MOVE_3D | MOVE_FULL: hipLaunchKernelGGL((k_move<T, false, false, MOVE_3D | MOVE_FULL>), dim3(blocks), dim3(BS), 0, st, a); break;
         case MOVE_3D | MOVE_FULL | MOVE_DISTMEM: hipLaunchKernelGGL((k_move<T, false, false, MOVE_3D | MOVE_FULL | MOVE_DISTMEM>), dim3(blocks), dim3(BS), 0, st, a); break;
@@ -2413,6 +2415,7 @@ struct Particles : IParticles {
     if (do_bcnd && distmem()) build_migrant_lists();
   }
   unsigned puddle_pending_blocks = 0; bool hold_big_list = false;
+  int last_move_kernel = 0;                  // (the k_move instantiation of the last launch, "raw_move_kernel": SPEC | PC << 4 | TURB << 5)
   void puddle_reduce_deferred() { if (puddle_pending_blocks) puddle_reduce(puddle_pending_blocks); puddle_pending_blocks = 0; }
   void puddle_reduce(unsigned blocks)
   {
@@ -3503,7 +3506,8 @@ struct Particles : IParticles {
     }
     else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
-    else if (s == "raw_cond_listed") {             // droplets that the last condensation substep handed to the reference's iterates (cond_list)
+    else if (s == "raw_move_kernel") v.assign(1, (unsigned long long)last_move_kernel);   // k_move<T, PC, TURB, SPEC>: SPEC | PC << 4 | TURB << 5
+    else if (s == "raw_cond_listed") {            // droplets that the last condensation substep handed to the reference's iterates (cond_list)
       unsigned long long c = 0;
       if (defer_cnt.p && defer_cnt.n >= size_t(DEFER_SHARDS * DEFER_CNT_STRIDE) && o.cond_solver == 0) {
         auto h = d2h(defer_cnt.p, size_t(DEFER_SHARDS * DEFER_CNT_STRIDE));

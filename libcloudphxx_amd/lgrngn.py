@@ -1259,6 +1259,12 @@ class particles_t:
         v = self.state_u64("raw_mode")
         return bool(v[0]), int(v[1]), cond_kernel(int(v[2])), dbg(int(v[3]))
 
+    def move_kernel(self):
+        """the k_move instantiation of the object's last move launch (lcx_get_state_u64 "raw_move_kernel"): (PC, TURB, SPEC), SPEC the
+        sum of 1 three-dimensional, 2 the full step's pass, 4 a slab with neighbours, 8 implicit"""
+        v = int(self.state_u64("raw_move_kernel")[0])
+        return bool(v & 16), bool(v & 32), v & 15
+
     def set_profiling(self, on):
         self._chk(self._f("set_profiling")(self._h, C.c_int(int(on))))
 
