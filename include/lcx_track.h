@@ -5,6 +5,7 @@
  * per-cell sums of lcx_diag.h and the three rates cannot give, at the cost of a gather of the tracked droplets only.  A header of its own
  * because lcx.h is the surface that the CPU oracle mirrors entry for entry (tests/test_abi.py), and the reference has nothing like it.
  * Off by default; an object that never enabled it, or disabled it, allocates and launches exactly what it did before.
+ * WHY a tracked droplet changed between two samples -- condensation, collection, chemistry, how many collisions -- is lcx_track_budget.h.
  *
  * The mark.  lcx_track_enable appends ONE attribute column, "track", to both storage sets, zeroed: of the object's real type, it holds
  * k + 1 for the droplet with track index k and 0 for every other droplet (k + 1 <= LCX_TRK_MAX = 2^20 is exact in float).  It travels

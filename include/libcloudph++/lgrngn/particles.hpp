@@ -21,6 +21,7 @@
 #include "../../lcx_cond_rates.h"
 #include "../../lcx_move_rates.h"
 #include "../../lcx_track.h"
+#include "../../lcx_track_budget.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -133,6 +134,21 @@ namespace libcloudphxx { namespace lgrngn {
     std::vector<double> rec, time;
     std::vector<unsigned long long> steps;
     double at(size_t s, track_field_t f, size_t k) const { return rec[(s * size_t(LCX_TRK_FIELDS) + size_t(f)) * n_tracked + k]; }
+  };
+  // the accumulators of particles_t<real_t, HIP>::track_budget (an extension as well; include/lcx_track_budget.h defines each)
+  enum track_budget_field_t
+  {
+    trb_cond_dr3 = LCX_TRB_COND_DR3, trb_coal_dr3 = LCX_TRB_COAL_DR3, trb_coal_drd3 = LCX_TRB_COAL_DRD3, trb_chem_drd3 = LCX_TRB_CHEM_DRD3,
+    trb_coal_dn = LCX_TRB_COAL_DN, trb_coal_gains = LCX_TRB_COAL_GAINS, trb_coal_gives = LCX_TRB_COAL_GIVES,
+    trb_fields = LCX_TRB_FIELDS
+  };
+  // what track_budget reads: the rows of the samples held, rows[(s * 7 + field) * n_tracked + k], and the accumulators as they stand
+  struct track_budget_t
+  {
+    size_t n_samples = 0, n_tracked = 0;
+    std::vector<double> rows, acc;
+    double at(size_t s, track_budget_field_t f, size_t k) const { return rows[(s * size_t(LCX_TRB_FIELDS) + size_t(f)) * n_tracked + k]; }
+    double now(track_budget_field_t f, size_t k) const { return acc[size_t(f) * n_tracked + k]; }
   };
 
   // the rows of one threshold of particles_t<real_t, HIP>::cond_rates (an extension without a reference counterpart; include/lcx_cond_rates.h
@@ -494,6 +510,22 @@ namespace libcloudphxx { namespace lgrngn {
       size_t got = 0;
       detail::lcx_check(lcx_track_read(pimpl->h, out.rec.data(), size_t(LCX_TRK_FIELDS) * out.n_tracked, out.n_tracked, out.steps.data(), out.time.data(),
                                        out.n_samples, &got, 0, reset ? 1 : 0));
+    }
+    // EXTENSION (include/lcx_track_budget.h): every tracked droplet's growth split into condensation, collection and chemistry, and its
+    // collisions counted.  Needs track_enable; every sample taken while it is on also holds a row of the seven accumulators.
+    void track_budget_enable() { detail::lcx_check(lcx_track_budget_enable(pimpl->h)); }
+    void track_budget_disable() { detail::lcx_check(lcx_track_budget_disable(pimpl->h)); }
+    void track_budget_info(int *enabled, unsigned long long *cond_passes = nullptr, unsigned long long *chem_passes = nullptr,
+                           unsigned long long *coal_passes = nullptr)
+    { detail::lcx_check(lcx_track_budget_info(pimpl->h, enabled, cond_passes, chem_passes, coal_passes)); }
+    void track_budget(track_budget_t &out)
+    {
+      detail::lcx_check(lcx_track_info(pimpl->h, nullptr, nullptr, &out.n_tracked, nullptr, &out.n_samples, nullptr, nullptr, nullptr));
+      out.rows.assign(std::max<size_t>(out.n_samples * size_t(LCX_TRB_FIELDS) * out.n_tracked, 1), 0.);
+      out.acc.assign(std::max<size_t>(size_t(LCX_TRB_FIELDS) * out.n_tracked, 1), 0.);
+      size_t got = 0;
+      detail::lcx_check(lcx_track_budget_read(pimpl->h, out.rows.data(), size_t(LCX_TRB_FIELDS) * out.n_tracked, out.n_tracked, out.n_samples, &got,
+                                              out.acc.data(), out.n_tracked, 0));
     }
 
   private:

@@ -18,7 +18,8 @@ DEPS = ["lcx_core.hip", "lcx_cond_wq.hip", "lcx_cond_wq.hpp", "lcx_kernels.hpp",
         os.path.join("..", "..", "include", "lcx_chem.h"), os.path.join("..", "..", "include", "lcx_state.h"),
         os.path.join("..", "..", "include", "lcx_diag.h"), os.path.join("..", "..", "include", "lcx_coal_rates.h"),
         os.path.join("..", "..", "include", "lcx_cond_rates.h"),
-        os.path.join("..", "..", "include", "lcx_move_rates.h"), os.path.join("..", "..", "include", "lcx_track.h")]
+        os.path.join("..", "..", "include", "lcx_move_rates.h"), os.path.join("..", "..", "include", "lcx_track.h"),
+        os.path.join("..", "..", "include", "lcx_track_budget.h")]
 
 
 def needs_build():

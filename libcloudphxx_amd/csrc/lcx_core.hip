@@ -32,6 +32,7 @@
 #include "../../include/lcx_cond_rates.h"
 #include "../../include/lcx_move_rates.h"
 #include "../../include/lcx_track.h"
+#include "../../include/lcx_track_budget.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -168,6 +169,11 @@ struct IParticles {
   virtual void track_sample() { not_built("track"); }
   virtual void track_info(int *, size_t *, size_t *, size_t *, size_t *, unsigned long long *, int *, unsigned long long *) { not_built("track"); }
   virtual void track_read(double *, size_t, size_t, unsigned long long *, double *, size_t, size_t *, bool, bool) { not_built("track"); }
+  // their budget (include/lcx_track_budget.h): refused where tracking is
+  virtual void track_budget_enable() { not_built("track"); }
+  virtual void track_budget_disable() { not_built("track"); }
+  virtual void track_budget_info(int *, unsigned long long *, unsigned long long *, unsigned long long *) { not_built("track"); }
+  virtual void track_budget_read(double *, size_t, size_t, size_t, size_t *, double *, size_t, bool) { not_built("track"); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -2031,6 +2037,7 @@ struct Particles : IParticles {
     if (every < 0) throw lcx_error("libcloudph++: track: every = " + std::to_string(every) + " < 0");
     if (ix_trk < 0 && n_ext >= MAX_EXT) throw lcx_error("libcloudph++: track: no free attribute column (all " + std::to_string(MAX_EXT) + " are in use)");
     HIPCHK(hipStreamSynchronize(st));              // (a kernel still queued may read what a new size re-allocates)
+    trb_off();                                     // (include/lcx_track_budget.h: starting over switches the budget off)
     if (ix_trk < 0) {
       A.ext[n_ext].alloc(cap);
       if (B.n.p) B.ext[n_ext].alloc(cap);          // (else alloc_attrs(B) makes it with the others)
@@ -2049,6 +2056,7 @@ struct Particles : IParticles {
   {
     trk_need("disable");
     HIPCHK(hipStreamSynchronize(st));
+    trb_off();
     --n_ext;                                       // (ix_trk == n_ext - 1: the last column)
     A.ext[ix_trk].release(); B.ext[ix_trk].release();
     ix_trk = -1; trk_every = 0; trk_stale = false;
@@ -2090,6 +2098,9 @@ struct Particles : IParticles {
     trk_refresh_slots();
     track_sample_arg<T> a{trk_slot_of.p, A.n.p, A.ext[ix_trk].p, A.x.p, A.y.p, A.z.p, A.rw2.p, A.rd3.p, A.kpa.p, A.vt.p, ijk.p, Tk.p, RH.p, rv.p, nphys, ncell};
     hipLaunchKernelGGL(k_track_sample<T>, dim3(nblk(trk_n)), dim3(BS), 0, st, uint32_t(trk_n), a, trk_buf.p + track::buf_offset(s, 0, 0, trk_max), trk_max);
+    if (trb_on)                                    // (include/lcx_track_budget.h: the accumulators as they stand, into the sample's row)
+      hipLaunchKernelGGL(k_track_budget_row, dim3(nblk(size_t(LCX_TRB_FIELDS) * trk_n)), dim3(BS), 0, st, trk_n, trk_max, (const double *)trb_acc.p,
+                         trb_rows.p + s * size_t(LCX_TRB_FIELDS) * trk_max);
   }
   void trk_after_step()
   {
@@ -2103,6 +2114,10 @@ struct Particles : IParticles {
     if (trk_n == n0 || !trk_ns) return;
     const size_t m = trk_ns * size_t(LCX_TRK_FIELDS) * (trk_n - n0);
     hipLaunchKernelGGL(k_track_absent, dim3(nblk(m)), dim3(BS), 0, st, trk_buf.p, trk_ns, n0, trk_n, trk_max);
+    if (trb_on) {
+      const size_t mb = trk_ns * size_t(LCX_TRB_FIELDS) * (trk_n - n0);
+      hipLaunchKernelGGL(k_track_budget_absent, dim3(nblk(mb)), dim3(BS), 0, st, trb_rows.p, trk_ns, n0, trk_n, trk_max);
+    }
   }
   void track_select(const lcx_diag_clause_t *clause, int n_clauses, const double *box, size_t max_count, size_t *n_selected) override
   {
@@ -2188,7 +2203,89 @@ struct Particles : IParticles {
         memcpy(out + s * sample_stride + size_t(f) * field_stride, trk_host.data() + (s * size_t(LCX_TRK_FIELDS) + size_t(f)) * trk_n, trk_n * sizeof(double));
     for (size_t s = 0; s < trk_ns; ++s) { if (steps) steps[s] = trk_steps[s]; if (time) time[s] = trk_times[s]; }
     if (n_samples) *n_samples = trk_ns;
-    if (reset) { trk_ns = 0; trk_dropped = 0; }
+    if (reset) { trk_ns = 0; trk_dropped = 0; }   // (the budget's rows are counted by trk_ns as well: emptied with the samples)
+  }
+  // ---- the budget of tracked droplets (include/lcx_track_budget.h): seven accumulators per track index, fed by passes of their own ----
+  // trb_begin ahead of a pass stores n, rw2, rd3 of every index (per index, so no permutation can invalidate them); trb_end behind it adds
+  // the differences.  Both find the slots again where the list is stale.  Off, or with nothing tracked, nothing below launches.
+  bool trb_on = false;
+  unsigned long long trb_cond_passes = 0, trb_chem_passes = 0, trb_coal_passes = 0;
+  DevBuf<double> trb_acc, trb_rows, trb_out; DevBuf<n_t> trb_n0; DevBuf<T> trb_w0, trb_d0; std::vector<double> trb_host;
+  void trb_need(const char *what) const { if (!trb_on) throw lcx_error(std::string("libcloudph++: track budget: ") + what + " while the budget is not enabled (lcx_track_budget_enable)"); }
+  void trb_off()
+  {
+    trb_on = false; trb_cond_passes = trb_chem_passes = trb_coal_passes = 0;
+    trb_acc.release(); trb_rows.release(); trb_out.release(); trb_n0.release(); trb_w0.release(); trb_d0.release(); trb_host = {};
+  }
+  void track_budget_enable() override
+  {
+    if (distmem()) throw lcx_error("libcloudph++: track on a decomposed domain is not built");
+    if (ix_trk < 0) throw lcx_error("libcloudph++: track budget: enable while tracking is not enabled (lcx_track_enable)");
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t per = size_t(LCX_TRB_FIELDS) * trk_max;
+    if (trb_acc.n != per) { trb_acc.release(); trb_acc.alloc(per); }
+    if (trb_rows.n != trk_cap * per) { trb_rows.release(); trb_rows.alloc(trk_cap * per); }
+    if (trb_n0.n != trk_max) { trb_n0.release(); trb_n0.alloc(trk_max); trb_w0.release(); trb_w0.alloc(trk_max); trb_d0.release(); trb_d0.alloc(trk_max); }
+    HIPCHK(hipMemsetAsync(trb_acc.p, 0, per * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(trb_n0.p, 0, trk_max * sizeof(n_t), st));
+    if (trk_ns && trk_n) {                         // (the samples held were taken without a budget: absent in their rows)
+      const size_t m = trk_ns * size_t(LCX_TRB_FIELDS) * trk_n;
+      hipLaunchKernelGGL(k_track_budget_absent, dim3(nblk(m)), dim3(BS), 0, st, trb_rows.p, trk_ns, size_t(0), trk_n, trk_max);
+    }
+    trb_on = true; trb_cond_passes = trb_chem_passes = trb_coal_passes = 0;
+  }
+  void track_budget_disable() override { trb_need("disable"); HIPCHK(hipStreamSynchronize(st)); trb_off(); }
+  void track_budget_info(int *enabled, unsigned long long *cond_passes, unsigned long long *chem_passes, unsigned long long *coal_passes) override
+  {
+    if (enabled) *enabled = trb_on ? 1 : 0;
+    if (cond_passes) *cond_passes = trb_cond_passes;
+    if (chem_passes) *chem_passes = trb_chem_passes;
+    if (coal_passes) *coal_passes = trb_coal_passes;
+  }
+  template <int FAM, bool FIRST> void trb_launch()
+  {
+    if (!trk_n) return;
+    trk_refresh_slots();
+    track_budget_arg<T> a{trk_slot_of.p, A.n.p, A.ext[ix_trk].p, A.rw2.p, A.rd3.p, nphys, trb_n0.p, trb_w0.p, trb_d0.p, trb_acc.p, trk_max};
+    hipLaunchKernelGGL((k_track_budget<T, FAM, FIRST>), dim3(nblk(trk_n)), dim3(BS), 0, st, uint32_t(trk_n), a);
+  }
+  template <int FAM> void trb_begin() { Range r(this, "track_budget"); trb_launch<FAM, true>(); }
+  template <int FAM> void trb_end()
+  {
+    Range r(this, "track_budget");
+    ++(FAM == TRB_COND ? trb_cond_passes : FAM == TRB_CHEM ? trb_chem_passes : trb_coal_passes);
+    trb_launch<FAM, false>();
+  }
+  void track_budget_read(double *out, size_t sample_stride, size_t field_stride, size_t cap_samples, size_t *n_samples, double *now, size_t now_stride,
+                         bool on_device) override
+  {
+    trb_need("read");
+    if (!out && !now) throw lcx_error("libcloudph++: track budget: out == NULL and now == NULL");
+    const size_t nf = size_t(LCX_TRB_FIELDS);
+    if (out) {
+      if (field_stride < trk_n) throw lcx_error("libcloudph++: track budget: field_stride (" + std::to_string(field_stride) + ") < n_tracked (" + std::to_string(trk_n) + ")");
+      if (sample_stride < nf * field_stride)
+        throw lcx_error("libcloudph++: track budget: sample_stride (" + std::to_string(sample_stride) + ") < " + std::to_string(nf) + " * field_stride (" + std::to_string(field_stride) + ")");
+      if (cap_samples < trk_ns) throw lcx_error("libcloudph++: track budget: cap_samples (" + std::to_string(cap_samples) + ") < the samples held (" + std::to_string(trk_ns) + ")");
+    }
+    if (now && now_stride < trk_n) throw lcx_error("libcloudph++: track budget: now_stride (" + std::to_string(now_stride) + ") < n_tracked (" + std::to_string(trk_n) + ")");
+    const size_t per = nf * trk_n, m_out = out ? trk_ns * per : 0, m_now = now ? per : 0;
+    if (on_device) {
+      if (m_out) hipLaunchKernelGGL(k_track_budget_read, dim3(nblk(m_out)), dim3(BS), 0, st, (const double *)trb_rows.p, trk_ns, trk_n, trk_max, out, sample_stride, field_stride);
+      if (m_now) hipLaunchKernelGGL(k_track_budget_read, dim3(nblk(m_now)), dim3(BS), 0, st, (const double *)trb_acc.p, size_t(1), trk_n, trk_max, now, nf * now_stride, now_stride);
+    } else if (m_out + m_now) {
+      trb_out.alloc(m_out + m_now); trb_host.resize(m_out + m_now);
+      if (m_out) hipLaunchKernelGGL(k_track_budget_read, dim3(nblk(m_out)), dim3(BS), 0, st, (const double *)trb_rows.p, trk_ns, trk_n, trk_max, trb_out.p, per, trk_n);
+      if (m_now) hipLaunchKernelGGL(k_track_budget_read, dim3(nblk(m_now)), dim3(BS), 0, st, (const double *)trb_acc.p, size_t(1), trk_n, trk_max, trb_out.p + m_out, per, trk_n);
+      HIPCHK(hipMemcpyAsync(trb_host.data(), trb_out.p, (m_out + m_now) * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    sync();
+    if (!on_device) {
+      if (m_out) for (size_t s = 0; s < trk_ns; ++s) for (size_t f = 0; f < nf; ++f)
+        memcpy(out + s * sample_stride + f * field_stride, trb_host.data() + (s * nf + f) * trk_n, trk_n * sizeof(double));
+      if (m_now) for (size_t f = 0; f < nf; ++f) memcpy(now + f * now_stride, trb_host.data() + m_out + f * trk_n, trk_n * sizeof(double));
+    }
+    if (n_samples) *n_samples = trk_ns;
   }
   void refresh_n_max()
   {
@@ -3149,6 +3246,7 @@ struct Particles : IParticles {
       hipLaunchKernelGGL(k_incloud_time<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, ijk.p, A.rd3.p, A.kpa.p, A.rw2.p, Tk.p, T(dt), A.ext[ix_ict].p);
     if (opts.cond) {
       if (cdr.on) cdr_before();                    // (include/lcx_cond_rates.h: rw2 as stored ahead of the first condensation launch)
+      if (trb_on) trb_begin<TRB_COND>();           // (include/lcx_track_budget.h: the tracked droplets' rw2 ahead of it)
       // (a measurement switch that names one of the per-substep kernels gets that kernel)
       constexpr unsigned per_substep_variants = LCX_DBG_COND_NO_FUSED_SUBSTEPS | LCX_DBG_COND_FOLD | LCX_DBG_COND_WQ | LCX_DBG_COND_BUDGET | LCX_DBG_COND_PROBE |
                                                 LCX_DBG_COND_LEAN_R3 | LCX_DBG_FINISH_STAGED | LCX_DBG_COND_NO_FOLD;
@@ -3164,10 +3262,13 @@ struct Particles : IParticles {
       }
       sstp_save();
       if (cdr.on) cdr_tally();                     // (behind the last substep, whichever kernels ran it)
+      if (trb_on) trb_end<TRB_COND>();
       if (!chem_now) { Range r(this, "sync_out"); sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); flush_sync_jobs(); }
     }
     if (chem_now) {                                // (after condensation, ahead of the results going out: particles_step.ipp:269-327)
+      if (trb_on) trb_begin<TRB_CHEM>();
       chem_step(opts);
+      if (trb_on) trb_end<TRB_CHEM>();
       Range r(this, "sync_out");
       if (opts.cond) { sync_out_arr(th, th_, ncell); sync_out_arr(rv, rv_, ncell); }
       if (opts.chem_dsl) for (int gs = 0; gs < CH_GAS; ++gs) sync_out_arr(amb[gs], chem_arg[gs], ncell);
@@ -3228,8 +3329,10 @@ struct Particles : IParticles {
     if (opts.sedi || opts.coal || opts.cond) coal_bound_armed = hskpng_vterm(false, want_bound);
     const bool bound_collected = coal_bound_armed;
     if (opts.coal) {
+      if (trb_on) trb_begin<TRB_COAL>();           // (include/lcx_track_budget.h: one launch ahead of the substeps, one behind each)
       for (int step = 0; step < sstp_coal; ++step) {
         coal(dt / sstp_coal, opts.turb_coal, step == 0);
+        if (trb_on) trb_end<TRB_COAL>();
         // (hskpng_vterm_invalid between the substeps: left to the next substep's ranking, which every droplet passes anyway)
         if (step + 1 != sstp_coal) { if (dbg(LCX_DBG_VTERM_INVALID_OWN_PASS)) hskpng_vterm(true); else vt_fix_pending = true; }
       }
@@ -4643,6 +4746,14 @@ int lcx_track_info(lcx_particles *h, int *enabled, size_t *max_tracked, size_t *
 int lcx_track_read(lcx_particles *h, double *out, size_t sample_stride, size_t field_stride, unsigned long long *steps, double *time, size_t cap_samples,
                    size_t *n_samples, int out_on_device, int reset)
 { LCX_TRY(H->track_read(out, sample_stride, field_stride, steps, time, cap_samples, n_samples, out_on_device != 0, reset != 0)) }
+// ---- their budget (include/lcx_track_budget.h) ----
+int lcx_track_budget_enable(lcx_particles *h) { LCX_TRY(H->track_budget_enable()) }
+int lcx_track_budget_disable(lcx_particles *h) { LCX_TRY(H->track_budget_disable()) }
+int lcx_track_budget_info(lcx_particles *h, int *enabled, unsigned long long *cond_passes, unsigned long long *chem_passes, unsigned long long *coal_passes)
+{ LCX_TRY(H->track_budget_info(enabled, cond_passes, chem_passes, coal_passes)) }
+int lcx_track_budget_read(lcx_particles *h, double *out, size_t sample_stride, size_t field_stride, size_t cap_samples, size_t *n_samples, double *now,
+                          size_t now_stride, int out_on_device)
+{ LCX_TRY(H->track_budget_read(out, sample_stride, field_stride, cap_samples, n_samples, now, now_stride, out_on_device != 0)) }
 // ---- condensation rates per cell (include/lcx_cond_rates.h) ----
 int lcx_cond_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->cond_rates_enable(r_thr, n_thr)) }
 int lcx_cond_rates_disable(lcx_particles *h) { LCX_TRY(H->cond_rates_disable()) }

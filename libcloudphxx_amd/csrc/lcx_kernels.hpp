@@ -5152,4 +5152,64 @@ __global__ void k_track_slots_apply(size_t m, const uint32_t *slot, uint32_t fir
 // the receivers of a recycling are new droplets: k_rcyc_apply has copied the donor's columns, the mark goes back to 0
 template <class T> __global__ void k_track_unmark(size_t m, const uint32_t *slot, T *mark) { const size_t t = gid(); if (t < m) mark[slot[t]] = T(0); }
 
+// ---- the budget of tracked droplets (include/lcx_track_budget.h): a lane per track index around a pass of condensation, chemistry or
+// coalescence.  The start values are kept per INDEX (n0 == 0: the index takes no part), the slot is found as k_track_sample finds it.
+// FIRST only stores the start values; otherwise the pass's differences are added to the index's accumulators (a lane owns its seven: plain
+// loads and stores, no atomics) and the values read become the start values of the next pass (coalescence: the next substep).
+enum { TRB_COND, TRB_CHEM, TRB_COAL };
+template <class T> struct track_budget_arg {
+  const uint32_t *slot_of; const n_t *n; const T *mark, *rw2, *rd3; size_t n_storage;
+  n_t *n0; T *w0, *d0; double *acc; size_t max_tracked;
+};
+__device__ __forceinline__ double trb_cube(double x) { return x * sqrt(x); }          // (the `cube` of coal_tally_event)
+template <class T, int FAM, bool FIRST>
+__global__ void k_track_budget(uint32_t n_tracked, track_budget_arg<T> a)
+{
+  const size_t k = gid(); if (k >= n_tracked) return;
+  const uint32_t s = a.slot_of[k];
+  n_t n1 = 0; T w1 = T(0), d1 = T(0);
+  if (s != track::NONE && s < a.n_storage && a.mark[s] == T(k + 1)) { n1 = a.n[s]; if (n1) { w1 = a.rw2[s]; d1 = a.rd3[s]; } }
+  if (!FIRST) {
+    const n_t n0 = a.n0[k];
+    if (n0) {
+      const T w0 = a.w0[k], d0 = a.d0[k];
+      const bool dw = n1 && w1 != w0, dd = n1 && d1 != d0;
+      double *acc = a.acc + k;
+      const size_t mt = a.max_tracked;
+      if (FAM == TRB_COND) { if (dw) acc[LCX_TRB_COND_DR3 * mt] += trb_cube(double(w1)) - trb_cube(double(w0)); }
+      else if (FAM == TRB_CHEM) { if (dd) acc[LCX_TRB_CHEM_DRD3 * mt] += double(d1) - double(d0); }
+      else {
+        if (dw) acc[LCX_TRB_COAL_DR3 * mt] += trb_cube(double(w1)) - trb_cube(double(w0));
+        if (dd) acc[LCX_TRB_COAL_DRD3 * mt] += double(d1) - double(d0);
+        if (n1 < n0) { acc[LCX_TRB_COAL_DN * mt] += double(n0 - n1); acc[LCX_TRB_COAL_GIVES * mt] += 1.; }
+        else if (n1 == n0 && (dw || dd)) acc[LCX_TRB_COAL_GAINS * mt] += 1.;
+      }
+    }
+  }
+  if (FIRST || FAM == TRB_COAL) { a.n0[k] = n1; a.w0[k] = w1; a.d0[k] = d1; }
+}
+// a sample's row: the accumulators of [0, n_tracked) as they stand
+__global__ void k_track_budget_row(size_t n_tracked, size_t max_tracked, const double *acc, double *row)
+{
+  const size_t i = gid(); if (i >= size_t(LCX_TRB_FIELDS) * n_tracked) return;
+  const size_t f = i / n_tracked, k = i - f * n_tracked;
+  row[f * max_tracked + k] = acc[f * max_tracked + k];
+}
+// NaN for the indices [k0, k1) in the rows [0, n_samples): what a selection leaves in the rows of the samples taken before it
+__global__ void k_track_budget_absent(double *rows, size_t n_samples, size_t k0, size_t k1, size_t max_tracked)
+{
+  const size_t w = k1 - k0, per = size_t(LCX_TRB_FIELDS) * w;
+  const size_t i = gid(); if (i >= n_samples * per) return;
+  const size_t s = i / per, f = (i - s * per) / w, k = k0 + (i - s * per) % w;
+  rows[(s * size_t(LCX_TRB_FIELDS) + f) * max_tracked + k] = __builtin_nan("");
+}
+// out[s * sample_stride + f * field_stride + k] for k < n_tracked: lcx_track_budget_read (the accumulators: n_samples = 1, src = acc)
+__global__ void k_track_budget_read(const double *src, size_t n_samples, size_t n_tracked, size_t max_tracked, double *out, size_t sample_stride, size_t field_stride)
+{
+  const size_t per = size_t(LCX_TRB_FIELDS) * n_tracked;
+  const size_t i = gid(); if (i >= n_samples * per) return;
+  const size_t s = i / per, f = (i - s * per) / n_tracked, k = (i - s * per) % n_tracked;
+  out[s * sample_stride + f * field_stride + k] = src[(s * size_t(LCX_TRB_FIELDS) + f) * max_tracked + k];
+}
+
 } // namespace lcx

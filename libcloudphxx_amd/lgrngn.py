@@ -486,6 +486,22 @@ def track_check(clauses, box=None, max_count=1, lib=None):
         raise RuntimeError(lib.lcx_last_error().decode())
 
 
+# ---- the budget of tracked droplets (include/lcx_track_budget.h)
+TRACK_BUDGET_FIELDS = ("cond_dr3", "coal_dr3", "coal_drd3", "chem_drd3", "coal_dn", "coal_gains", "coal_gives")      # enum LCX_TRB_*, in its order
+
+
+def track_budget_check_out(out, n_samples, n_tracked):
+    """refuses an `out` of track_budget that is no DeviceArray of (n_samples, 7, n_tracked) doubles with unit stride along the droplets"""
+    nf = len(TRACK_BUDGET_FIELDS)
+    if out is None:
+        return
+    if not isinstance(out, DeviceArray) or len(out.shape) != 3 or tuple(out.shape) != (n_samples, nf, n_tracked):
+        raise ValueError("libcloudph++: track budget: out must be a DeviceArray of shape (n_samples, %d, n_tracked) = (%d, %d, %d)"
+                         % (nf, n_samples, nf, n_tracked))
+    if n_tracked > 1 and out.strides[2] != 1:
+        raise ValueError("libcloudph++: track budget: out must have unit stride along the droplets")
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -1153,6 +1169,45 @@ class particles_t:
         res = {"steps": steps[:ns].copy(), "time": time[:ns].copy()}
         if out is None:
             for f, nm in enumerate(TRACK_FIELDS):
+                res[nm] = arr[:ns, f, :nt].copy()
+        return res
+
+    # -- the budget of tracked droplets (include/lcx_track_budget.h)
+    def track_budget_enable(self):
+        """from now on every tracked droplet's growth is split by process (TRACK_BUDGET_FIELDS); needs track_enable"""
+        self._chk(self._f("track_budget_enable")(self._h))
+
+    def track_budget_disable(self):
+        self._chk(self._f("track_budget_disable")(self._h))
+
+    def track_budget_info(self):
+        """dict: enabled, cond_passes, chem_passes, coal_passes"""
+        en, cd, ch, co = C.c_int(), C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        self._chk(self._f("track_budget_info")(self._h, C.byref(en), C.byref(cd), C.byref(ch), C.byref(co)))
+        return {"enabled": en.value, "cond_passes": cd.value, "chem_passes": ch.value, "coal_passes": co.value}
+
+    def track_budget(self, out=None):
+        """the rows of the samples held: a dict with one (n_samples, n_tracked) float64 array per name of TRACK_BUDGET_FIELDS, plus "now":
+        {name: (n_tracked,) array}, the accumulators as they stand.  With out= (a DeviceArray of the object's device, (n_samples, 7,
+        n_tracked) doubles with unit stride along the droplets) the rows go there instead and the dict holds "now" only."""
+        info = self.track_info()
+        ns, nt, nf = info["n_samples"], info["n_tracked"], len(TRACK_BUDGET_FIELDS)
+        track_budget_check_out(out, ns, nt)
+        now = np.zeros((nf, max(nt, 1)), dtype=np.float64)
+        nowp = now.ctypes.data_as(C.POINTER(C.c_double))
+        got = C.c_size_t()
+        call = self._f("track_budget_read")
+        if out is None:
+            arr = np.zeros((max(ns, 1), nf, max(nt, 1)), dtype=np.float64)
+            self._chk(call(self._h, C.c_void_p(arr.ctypes.data), C.c_size_t(nf * max(nt, 1)), C.c_size_t(max(nt, 1)), C.c_size_t(max(ns, 1)), C.byref(got),
+                           nowp, C.c_size_t(max(nt, 1)), C.c_int(0)))
+        else:                                                                 # (the accumulators come to the host all the same: a call of their own)
+            self._chk(call(self._h, C.c_void_p(out.ptr), C.c_size_t(out.strides[0]), C.c_size_t(out.strides[1]), C.c_size_t(ns), C.byref(got),
+                           None, C.c_size_t(0), C.c_int(1)))
+            self._chk(call(self._h, None, C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.byref(got), nowp, C.c_size_t(max(nt, 1)), C.c_int(0)))
+        res = {"now": {nm: now[f, :nt].copy() for f, nm in enumerate(TRACK_BUDGET_FIELDS)}}
+        if out is None:
+            for f, nm in enumerate(TRACK_BUDGET_FIELDS):
                 res[nm] = arr[:ns, f, :nt].copy()
         return res
 
