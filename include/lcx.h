@@ -246,6 +246,10 @@ enum lcx_dbg2 {
   LCX_DBG2_COAL_CELL_LIST_ALWAYS = 1 << 5, /* tests: the list form in every launch that is handed the flags, the first one and a crowded vote included; the vote's counts
                                         * then pause neither the bound nor the exit */
   LCX_DBG2_COAL_CELL_LIST_SMALL = 1 << 6, /* tests: k_coal_cells on one workgroup, and cells above 64 droplets ranked by counting in memory */
+  LCX_DBG2_NO_COAL_CMAX_FLOOR = 1 << 7, /* the cell maxima of the bound start from zero and every droplet offers to them, as in round 11, instead of starting
+                                        * from a floor below which no droplet offers (the same bits).  "raw_coal_cmax" = the 2 x n_cell words of the last
+                                        * velocity pass that collected maxima, "raw_coal_cmax_floor" = the two words they started from */
+  LCX_DBG2_COAL_CMAX_FLOOR_HIGH = 1 << 8, /* tests: the floor at a bound of 2^-6 instead of the production value */
   LCX_DBG2_NO_COAL_PREVOTE = 1 << 3    /* the form with the exit without the per-cell vote ahead of the launch (k_coal_umin, k_coal_cellvote): every workgroup
                                         * loads its cells' numbers, draws and votes for itself, as in round 9 (the same bits).  "raw_coal_prevote" = { launches
                                         * of the last lcx_step_async that were handed the tiles' flags, tiles flagged off, tiles, launches that fell back because

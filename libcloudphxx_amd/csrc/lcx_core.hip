@@ -36,6 +36,7 @@
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
+#include "lcx_coal_floor_probe.h"
 
 // every kernel launch of this translation unit and every host wait for a stream are COUNTED (lcx_get_state_u64 "raw_launches"): what a
 // step costs a thin slab or a 2-D set-up is its launches and its waits, not its bytes (bench.py's c2 leg reports both per step)
@@ -433,6 +434,8 @@ struct Particles : IParticles {
   DevBuf<n_t> coal_n_max;                    // the largest multiplicity in storage ...
   bool n_max_stale = true;                   // ... to be recomputed: something other than coalescence has written multiplicities (init, set_particles,
                                              // a source, relaxation, recycling, immigrants) -- coalescence itself only lowers them
+  DevBuf<uint32_t> coal_floor;               // the floor pair under coal_cmax ("raw_coal_cmax_floor"; refresh_cmax_floor)
+  bool floor_stale = true; double floor_dt = -1; size_t floor_occ = 0;
   DevBuf<T> coal_emax; int n_emax = 0;       // the efficiency table's running maximum by kernel_index (init_kernel); 0: no bound for this kernel
   DevBuf<unsigned long long> coal_skip_cnt;  // LCX_DBG2_COAL_SKIP_COUNT: {pairs skipped, pairs examined, workgroups that left before ranking, workgroups
                                              // launched} of the last step_async ("raw_coal_skip", "raw_coal_wg")
@@ -1224,12 +1227,13 @@ struct Particles : IParticles {
         vtpre_valid = true;
       }
       const dim3 gv(nblk(nphys, 2 * BS * VT_CHUNKS));                   // VT_CHUNKS pairs of super-droplets per lane
-      auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, (uint32_t *)nullptr); };
+      auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, (uint32_t *)nullptr, (const uint32_t *)nullptr); };
       const bool table = vtc.formula == LCX_VT_BEARD77FAST;
       if (cell_max && !only_invalid) {
         coal_cmax.alloc(2 * ncell);
-        HIPCHK(hipMemsetAsync(coal_cmax.p, 0, 2 * ncell * sizeof(uint32_t), st));
-        auto launch_max = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, 0, vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, coal_cmax.p); };
+        refresh_cmax_floor();                          // (the maxima start from the floor pair, and the pass offers only above it)
+        hipLaunchKernelGGL(k_fill_pairs, dim3(nblk(ncell)), dim3(BS), 0, st, coal_cmax.p, size_t(ncell), (const uint32_t *)coal_floor.p);
+        auto launch_max = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, 0, vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, coal_cmax.p, (const uint32_t *)coal_floor.p); };
         if (o.strict_fp) { if (table) launch_max(k_vterm_b77<T, false, true, true>); else launch_max(k_vterm_b77<T, false, false, true>); }
         else             { if (table) launch_max(k_vterm_b77<T, true, true, true>); else launch_max(k_vterm_b77<T, true, false, true>); }
         return true;
@@ -2293,7 +2297,23 @@ struct Particles : IParticles {
     coal_n_max.alloc(1);
     HIPCHK(hipMemsetAsync(coal_n_max.p, 0, sizeof(n_t), st));
     if (nphys) hipLaunchKernelGGL(k_n_max, dim3(std::min(nblk(nphys), 2048u)), dim3(BS), 0, st, nphys, (const n_t *)A.n.p, coal_n_max.p);
-    n_max_stale = false;
+    n_max_stale = false; floor_stale = true;
+  }
+  // The floor under the cell maxima (lcx_coal_prevote.hpp coal_cmax_floor), computed on the device from *coal_n_max with no host wait: again
+  // wherever the largest multiplicity was recomputed, and where the coalescence substep or the mean occupancy has changed.  The reference
+  // cell is the middle one, the reference scale factor the mean occupancy's (any floor is sound; the occupancy is followed so that the floor
+  // is a function of the object's state alone, the same in a restored object).  LCX_DBG2_NO_COAL_CMAX_FLOOR: zeros, every droplet offers.
+  // Called by the armed velocity pass alone, which step_async launches behind refresh_n_max(): *coal_n_max is current.
+  void refresh_cmax_floor()
+  {
+    const double dt_sub = dt / sstp_coal;
+    const size_t occ = std::max<size_t>(2, (npart + ncell - 1) / std::max<size_t>(ncell, 1));
+    if (!floor_stale && coal_floor.p && floor_dt == dt_sub && floor_occ == occ) return;
+    coal_floor.alloc(2);
+    if (dbg2(LCX_DBG2_NO_COAL_CMAX_FLOOR)) HIPCHK(hipMemsetAsync(coal_floor.p, 0, 2 * sizeof(uint32_t), st));
+    else hipLaunchKernelGGL(k_coal_floor<T>, dim3(1), dim3(WAVE), 0, st, (const n_t *)coal_n_max.p, (const T *)dv.p, size_t(ncell / 2), coal_scale_of<T>(n_t(occ)),
+                            T(dt_sub), T(kernel_r_max), (const T *)coal_emax.p, n_emax, T(dbg2(LCX_DBG2_COAL_CMAX_FLOOR_HIGH) ? COAL_FLOOR_EPS_HIGH : COAL_FLOOR_EPS), coal_floor.p);
+    floor_stale = false; floor_dt = dt_sub; floor_occ = occ;
   }
   // step_async, ahead of the velocity pass: the smallest draw of every cell's pairs, on the side stream (beside that pass: it waits for memory, this
   // kernel only multiplies integers).  Launched where the step's first coalescence launch will be the EXIT form as far as can be known here; the call
@@ -2357,11 +2377,11 @@ struct Particles : IParticles {
           if (pv_call_of == rs.call && pv_seed_of == rs.seed && pv_cells_of == cells_version && pv_npart_of == npart) {
             coal_tile_flag.alloc(gr.x);
             HIPCHK(hipMemsetAsync(coal_tile_flag.p, 0, size_t(gr.x) * sizeof(uint32_t), st));
-            coal_vote_out vo{nullptr, nullptr};
+            coal_vote_out vo{nullptr, nullptr, 0};
             if (!dbg2(LCX_DBG2_NO_COAL_CELL_LIST)) {                 // (the vote also lists the kept cells and counts what the host chooses the form by)
-              coal_kept_cells.alloc(ncell); coal_vote_cnt.alloc(CV_WORDS);
+              coal_kept_cells.alloc(CV_SLOTS * coal_sublist_cap(ncell, WAVE)); coal_vote_cnt.alloc(CV_WORDS);
               HIPCHK(hipMemsetAsync(coal_vote_cnt.p, 0, CV_WORDS * sizeof(unsigned long long), st));
-              vo = coal_vote_out{coal_kept_cells.p, coal_vote_cnt.p};
+              vo = coal_vote_out{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE)};
             }
             cells_listed = vo.list != nullptr;
             hipLaunchKernelGGL(k_coal_cellvote<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const uint32_t *)cell_start.p, (const uint32_t *)coal_cmax.p, (const T *)dv.p,
@@ -2390,7 +2410,7 @@ struct Particles : IParticles {
                              deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
         };
         if (by_cells) {
-          const coal_cells_args ca{coal_kept_cells.p, coal_vote_cnt.p + CV_KEPT, coal_cmax.p, coal_n_max.p, n_emax,
+          const coal_cells_args ca{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE), coal_cmax.p, coal_n_max.p, n_emax,
                                    dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? uint32_t(WAVE) : uint32_t(CELLRANK_MAX)};
           const dim3 gc(unsigned(coal_cells_grid(ncell, COAL_CELLS_WAVES, dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? 1 : COAL_CELLS_GRID_CAP)));
           auto launch_cells = [&](auto kern) {
@@ -3607,6 +3627,18 @@ struct Particles : IParticles {
       v.assign(3, 0ull); v[0] = (unsigned long long)last_coal_cells;
       if (cells_listed) { auto h = d2h(coal_vote_cnt.p, CV_WORDS); const coal_vote_sums cv = coal_vote_sums_of(h.data()); v[1] = cv.kept; v[2] = cv.with_pair; }
     }
+    else if (s == "raw_coal_kept_list") {          // the kept cells of the last step_async's vote, sub-list by sub-list (no list: empty)
+      if (cells_listed) {
+        auto h = d2h(coal_vote_cnt.p, CV_WORDS); auto l = d2h(coal_kept_cells.p, CV_SLOTS * coal_sublist_cap(ncell, WAVE));
+        for (int i = 0; i < CV_SLOTS; ++i) for (unsigned long long j = 0; j < h[CV_SLOT0 + i * CV_SLOT_WORDS + CVS_LIST]; ++j) v.push_back(l[i * coal_sublist_cap(ncell, WAVE) + j]);
+      }
+    }
+    else if (s == "raw_coal_cmax") {               // the 2 x n_cell words of the last armed velocity pass (none yet: empty)
+      if (coal_cmax.p && coal_cmax.n >= 2 * ncell) { auto h = d2h(coal_cmax.p, 2 * ncell); v.assign(h.begin(), h.end()); }
+    }
+    else if (s == "raw_coal_cmax_floor") {         // the floor pair that pass was armed with
+      if (coal_floor.p) { auto h = d2h(coal_floor.p, 2); v.assign(h.begin(), h.end()); }
+    }
     else if (s == "raw_coal_bound_unused") v.assign(1, coal_bound_unused);
     else if (s == "raw_coal_kernel") v.assign(1, (unsigned long long)last_coal_kernel);   // 0 k_coal<T, false>, 1 k_coal<T, true>, 2 k_coal<T, false, true>
     else if (s == "raw_move_kernel") v.assign(1, (unsigned long long)last_move_kernel);   // k_move<T, PC, TURB, SPEC>: SPEC | PC << 4 | TURB << 5
@@ -4655,6 +4687,12 @@ int lcx_set_state_real(lcx_particles *h, const char *name, const double *data, s
 int lcx_stage(lcx_particles *h, const char *stage, const lcx_opts_t *o) { LCX_TRY(H->stage(stage, o)) }
 int lcx_timings(lcx_particles *h, const char **names, double *ms, size_t cap, size_t *n) { LCX_TRY(H->timings(names, ms, cap, n)) }
 int lcx_set_profiling(lcx_particles *h, int on) { LCX_TRY(H->set_profiling(on)) }
+// (declared in lcx_coal_floor_probe.h, not in include/lcx.h, whose surface the oracle mirrors: a probe for tools/coal_floor_gate.py)
+void lcx_coal_cmax_floor(double dt, double dvc, double scl, double n_max, double r_max, const double *emax, int n_emax, double eps, unsigned *words)
+{
+  const lcx::coal_floor_words w = lcx::coal_cmax_floor<double>(dt, dvc, scl, n_max, r_max, emax, n_emax, eps > 0 ? eps : lcx::COAL_FLOOR_EPS);
+  words[0] = w.r_bits; words[1] = w.v_bits;
+}
 int lcx_migrate_counts(lcx_particles *h, size_t *l, size_t *r) { LCX_TRY(H->migrate_counts(l, r)) }
 size_t lcx_migrate_record_bytes(lcx_particles *h) { DevGuard dev_guard_; return H->migrate_record_bytes(); }
 int lcx_migrate_pack(lcx_particles *h, int side, double x_rmt, void *buf, size_t cap) { LCX_TRY(H->migrate_pack(side, x_rmt, buf, cap)) }

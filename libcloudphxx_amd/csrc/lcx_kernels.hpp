@@ -1026,31 +1026,26 @@ __device__ __forceinline__ bool vterm_b77_one(const vt_cfg &v, T r2, uint32_t c,
 constexpr int VT_CHUNKS = 2;
 // Round 8, CELLMAX (the all-droplets pass ahead of a coalescence that ranks for itself, lcx_core.hip coal_skip_wanted; off everywhere else): the
 // pass also leaves, per cell, the largest wet radius squared and the largest velocity among the droplets it writes, each as the bits of a float
-// rounded UP (positive floats order as unsigned integers) in cmax[2 c] and cmax[2 c + 1], cleared by the host -- what coal_pair's bound on a
-// pair's collision probability is made of.  A living droplet that the pass does not evaluate, or a velocity that is not >= 0, writes all-ones
-// bits (a NaN, and the largest unsigned): nothing is skipped in that cell.
-// Not a global atomic per droplet: every droplet offers its bits to a table of CM_SLOTS cells in the workgroup's LDS (open addressing on a
-// multiplicative hash of the cell, four probes, then straight to memory), with LDS atomics that return nothing but the claim of a slot; behind
-// a barrier each used slot leaves as two non-returning global atomics.  A workgroup's 1024 neighbours in storage lie in a few dozen cells.
-// (Measured and dropped: the lanes of a wave grouped by cell with ballots as in wave_hist_rank and reduced with DPP, one round per cell -- the
-// pass at 1.27 ms against 0.69 without the maxima, with or without its global atomics: a wave meets a dozen cells and more, and sixty
-// instructions per round double what the pass issues.)
-constexpr uint32_t CMAX_POISON = 0xFFFFFFFFu, CMAX_FLOOR = 0x00800000u;      // (FLT_MIN: a recorded maximum is never zero or subnormal)
-template <class T>
-__device__ __forceinline__ uint32_t float_bits_up(T x)                         // x > 0 (infinity included)
-{
-  const float f = float(x);
-  uint32_t b = __float_as_uint(f);
-  if (T(f) < x) ++b;                                                          // rounded down: the next float up
-  return b < CMAX_FLOOR ? CMAX_FLOOR : b;
-}
-constexpr int CM_BITS = 8, CM_SLOTS = 1 << CM_BITS;
-struct cellmax_lds { uint32_t key[CM_SLOTS], r[CM_SLOTS], v[CM_SLOTS]; };
+// rounded UP (positive floats order as unsigned integers) in cmax[2 c] and cmax[2 c + 1] -- what coal_pair's bound on a pair's collision
+// probability is made of.  A living droplet that the pass does not evaluate, or a velocity that is not >= 0, writes all-ones bits (a NaN, and
+// the largest unsigned): nothing is skipped in that cell.  (CMAX_POISON, CMAX_FLOOR and float_bits_up: lcx_coal_prevote.hpp, shared with the host.)
+// Round 12, THE FLOOR: the host arms cmax with the floor pair fl[0], fl[1] (lcx_coal_prevote.hpp coal_cmax_floor, computed on the device) instead
+// of zeros, and a droplet offers only where one of its words is above the floor's -- integer compares; CMAX_POISON is above by construction, so
+// a living droplet that the pass does not evaluate still poisons its cell.  A few droplets in a hundred are left (EXPERIMENTS.md 7.21).
+// A WAVE none of whose droplets offers is done: it has stored its velocities as the plain pass does, and touches no LDS.  A wave with an offer
+// clears a table of WAVE cells of its own in LDS (open addressing on a multiplicative hash of the cell, four probes, then straight to memory),
+// the lanes above the floor offer with LDS atomics that return nothing but the claim of a slot, and each used slot leaves as two non-returning
+// global atomics.  Wave fences only: no workgroup barrier, no wave waits for another.
+// (Round 8 to 11: every droplet offered to ONE table of 256 cells per workgroup between two barriers, the velocities stored behind them; 1.05 ms
+// against 0.69 without the maxima.  Measured and dropped, 7.21: that table with the floor; no table and a global atomic pair per droplet above the
+// floor; the offers of a wave reduced cell by cell with ballots and a butterfly -- a wave meets a dozen cells and more.)
+constexpr int CMW_BITS = 6;
+struct cellmax_lds { uint32_t key[1 << CMW_BITS], r[1 << CMW_BITS], v[1 << CMW_BITS]; };
 __device__ __forceinline__ void cellmax_offer(uint32_t *cmax, cellmax_lds &t, uint32_t c, uint32_t r, uint32_t v)
 {
-  uint32_t s = (c * 2654435761u) >> (32 - CM_BITS);
+  uint32_t s = (c * 2654435761u) >> (32 - CMW_BITS);
 #pragma unroll 1
-  for (int probe = 0; probe < 4; ++probe, s = (s + 1) & (CM_SLOTS - 1)) {
+  for (int probe = 0; probe < 4; ++probe, s = (s + 1) & ((1 << CMW_BITS) - 1)) {
     uint32_t prev = t.key[s];
     if (prev == CMAX_POISON) prev = atomicCAS(&t.key[s], CMAX_POISON, c);
     if (prev == CMAX_POISON || prev == c) { atomicMax(&t.r[s], r); atomicMax(&t.v[s], v); return; }
@@ -1059,13 +1054,15 @@ __device__ __forceinline__ void cellmax_offer(uint32_t *cmax, cellmax_lds &t, ui
 }
 template <class T, bool FAST, bool TABLE, bool CELLMAX = false>
 __global__ void __launch_bounds__(BS)
-k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *ijk, const beard77_cell<T> *pre, const T *vt_0, T *vt, uint32_t *cmax = nullptr)
+k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *ijk, const beard77_cell<T> *pre, const T *vt_0, T *vt, uint32_t *cmax = nullptr,
+            const uint32_t *fl = nullptr)
 {
   struct alignas(2 * sizeof(T)) pairT { T a, b; };
   struct alignas(8) pairU { uint32_t a, b; };
-  __shared__ cellmax_lds cm[1];                     // (unused, and dropped by the compiler, without CELLMAX)
-  static_assert(CM_SLOTS == BS, "a slot per thread");
-  if constexpr (CELLMAX) { cm[0].key[threadIdx.x] = CMAX_POISON; cm[0].r[threadIdx.x] = 0u; cm[0].v[threadIdx.x] = 0u; }
+  __shared__ cellmax_lds cm[BS / WAVE];             // (a table per wave; unused, and dropped by the compiler, without CELLMAX)
+  static_assert((1 << CMW_BITS) == WAVE, "a slot per lane");
+  [[maybe_unused]] coal_floor_words floor_w{CMAX_FLOOR, CMAX_FLOOR};
+  if constexpr (CELLMAX) floor_w = coal_floor_words{fl[0], fl[1]};
   const size_t base = size_t(blockIdx.x) * (2 * BS * VT_CHUNKS) + 2 * threadIdx.x;
   pairT r2[VT_CHUNKS], o[VT_CHUNKS]; pairU c[VT_CHUNKS];
 #pragma unroll
@@ -1079,12 +1076,10 @@ k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *
     else { r2[k] = pairT{T(0), T(0)}; c[k] = pairU{DEAD_CELL, DEAD_CELL}; o[k] = r2[k]; }
   }
   // CELLMAX: the bits that each slot offers to its cell's maxima (a living droplet that is not evaluated: all ones)
-  // (CELLMAX stores the velocities BEHIND the maxima: a wave waits for its stores in flight before it may reuse their registers)
   [[maybe_unused]] uint32_t mr[VT_CHUNKS][2], mv[VT_CHUNKS][2];
-  [[maybe_unused]] pairT res[VT_CHUNKS]; [[maybe_unused]] bool sa[VT_CHUNKS], sb[VT_CHUNKS];
   if constexpr (CELLMAX) {
 #pragma unroll
-    for (int k = 0; k < VT_CHUNKS; ++k) { mr[k][0] = mr[k][1] = mv[k][0] = mv[k][1] = CMAX_POISON; sa[k] = sb[k] = false; }
+    for (int k = 0; k < VT_CHUNKS; ++k) mr[k][0] = mr[k][1] = mv[k][0] = mv[k][1] = CMAX_POISON;
   }
 #pragma unroll
   for (int k = 0; k < VT_CHUNKS; ++k) {
@@ -1093,41 +1088,58 @@ k_vterm_b77(size_t n, int only_invalid, vt_cfg v, const T *rw2, const uint32_t *
     T va = o[k].a, vb = o[k].b;
     const bool wa = !(only_invalid && !(va == T(-1))) && vterm_b77_one<T, FAST, TABLE>(v, r2[k].a, c[k].a, pre, vt_0, va);
     const bool wb = i + 1 < n && !(only_invalid && !(vb == T(-1))) && vterm_b77_one<T, FAST, TABLE>(v, r2[k].b, c[k].b, pre, vt_0, vb);
-    if constexpr (!CELLMAX) {
-      if (wa && wb) *reinterpret_cast<pairT *>(vt + i) = pairT{va, vb};
-      else if (wa) vt[i] = va;
-      else if (wb) vt[i + 1] = vb;
-    } else {
-      res[k] = pairT{va, vb}; sa[k] = wa; sb[k] = wb;
+    if (wa && wb) *reinterpret_cast<pairT *>(vt + i) = pairT{va, vb};
+    else if (wa) vt[i] = va;
+    else if (wb) vt[i + 1] = vb;
+    if constexpr (CELLMAX) {
       if (wa) { mr[k][0] = float_bits_up(r2[k].a); mv[k][0] = va > T(0) ? float_bits_up(va) : va == T(0) ? CMAX_FLOOR : CMAX_POISON; }
       if (wb) { mr[k][1] = float_bits_up(r2[k].b); mv[k][1] = vb > T(0) ? float_bits_up(vb) : vb == T(0) ? CMAX_FLOOR : CMAX_POISON; }
     }
   }
-  if constexpr (CELLMAX) {                             // (behind the loop: every thread of the workgroup is here; slots past n carry DEAD_CELL)
-    __syncthreads();                                   // (the table is cleared)
+  if constexpr (CELLMAX) {                             // (behind the loop: every lane of the wave is here; slots past n carry DEAD_CELL)
+    bool offers[VT_CHUNKS][2], any = false;
 #pragma unroll
     for (int k = 0; k < VT_CHUNKS; ++k) {
-      const bool la = c[k].a != DEAD_CELL, lb = c[k].b != DEAD_CELL;
-      if (la && lb && c[k].a == c[k].b)                // (neighbours in storage, mostly of one cell: one offer)
-        cellmax_offer(cmax, cm[0], c[k].a, mr[k][0] > mr[k][1] ? mr[k][0] : mr[k][1], mv[k][0] > mv[k][1] ? mv[k][0] : mv[k][1]);
-      else {
-        if (la) cellmax_offer(cmax, cm[0], c[k].a, mr[k][0], mv[k][0]);
-        if (lb) cellmax_offer(cmax, cm[0], c[k].b, mr[k][1], mv[k][1]);
+      if (c[k].a == c[k].b) {                          // (neighbours in storage, mostly of one cell: one offer)
+        if (mr[k][1] > mr[k][0]) mr[k][0] = mr[k][1];
+        if (mv[k][1] > mv[k][0]) mv[k][0] = mv[k][1];
+        c[k].b = DEAD_CELL;
       }
+      offers[k][0] = c[k].a != DEAD_CELL && coal_above_floor(mr[k][0], mv[k][0], floor_w);
+      offers[k][1] = c[k].b != DEAD_CELL && coal_above_floor(mr[k][1], mv[k][1], floor_w);
+      any = any || offers[k][0] || offers[k][1];
     }
-    __syncthreads();
-    {
-      const uint32_t cell = cm[0].key[threadIdx.x];
-      if (cell != CMAX_POISON) { atomicMax(&cmax[2 * size_t(cell)], cm[0].r[threadIdx.x]); atomicMax(&cmax[2 * size_t(cell) + 1], cm[0].v[threadIdx.x]); }
-    }
+    if (__ballot(any)) {                               // (uniform)
+      auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+      cellmax_lds &t = cm[wave_id()];
+      const uint32_t lane = lane_id();
+      t.key[lane] = CMAX_POISON; t.r[lane] = 0u; t.v[lane] = 0u;
+      wave_sync();
 #pragma unroll
-    for (int k = 0; k < VT_CHUNKS; ++k) {
-      const size_t i = base + size_t(k) * 2 * BS;
-      if (sa[k] && sb[k]) *reinterpret_cast<pairT *>(vt + i) = res[k];
-      else if (sa[k]) vt[i] = res[k].a;
-      else if (sb[k]) vt[i + 1] = res[k].b;
+      for (int k = 0; k < VT_CHUNKS; ++k) {
+        if (offers[k][0]) cellmax_offer(cmax, t, c[k].a, mr[k][0], mv[k][0]);
+        if (offers[k][1]) cellmax_offer(cmax, t, c[k].b, mr[k][1], mv[k][1]);
+      }
+      wave_sync();
+      const uint32_t cell = t.key[lane];
+      if (cell != CMAX_POISON) { atomicMax(&cmax[2 * size_t(cell)], t.r[lane]); atomicMax(&cmax[2 * size_t(cell) + 1], t.v[lane]); }
     }
   }
+}
+// the floor under the maxima (lcx_coal_prevote.hpp coal_cmax_floor) from the largest multiplicity as it stands on the device, one thread, no host
+// wait: fl[0], fl[1]; and the maxima armed with it ahead of the pass, a pair of words per cell
+template <class T>
+__global__ void k_coal_floor(const n_t *n_max, const T *dv, size_t ref_cell, T scl, T dt, T r_max, const T *emax, int n_emax, T eps, uint32_t *fl)
+{
+  if (gid() != 0) return;
+  const coal_floor_words w = coal_cmax_floor<T>(dt, dv[ref_cell], scl, T(*n_max), r_max, emax, n_emax, eps);
+  fl[0] = w.r_bits; fl[1] = w.v_bits;
+}
+__global__ void __launch_bounds__(BS) k_fill_pairs(uint32_t *a, size_t n_pairs, const uint32_t *pair)
+{
+  struct alignas(8) pairU { uint32_t a, b; };
+  const size_t i = gid();
+  if (i < n_pairs) reinterpret_cast<pairU *>(a)[i] = pairU{pair[0], pair[1]};
 }
 // the largest multiplicity in storage (the third factor of coal_pair's bound; coalescence only lowers multiplicities, so the host computes it
 // only after something else has written them)
@@ -3006,21 +3018,25 @@ k_coal_umin(size_t n_cell, const uint32_t *cell_start, uint64_t call, uint64_t s
 // table's end) fails the comparison and keeps the cell.  A cell without a pair keeps nothing.
 // Round 11: THE VOTE ALSO LEAVES A LIST (vo.list != nullptr): every kept cell's index is appended to vo.list (room for n_cell), in the order the waves'
 // atomics arrive -- nobody may rely on it, a cell's pairs touch that cell's droplets alone -- and vo.cnt counts what the host decides from
-// (lcx_core.hip poll_cells_vote): kept cells (the list's length, word CV_KEPT), and cells with a pair, pairs, pairs in kept cells and tiles flagged
+// (lcx_core.hip poll_cells_vote): kept cells (the list's length), and cells with a pair, pairs, pairs in kept cells and tiles flagged
 // on.  One atomic per wave and counter that the wave adds to.  Every wave with a pair adds to the middle two, and 33 000 waves adding to one word
 // took 0.1 ms at 64^3 cells (12 ns an atomic, one behind the other in the L2; EXPERIMENTS.md 7.17): those four are kept in CV_SLOTS copies, a
 // cache line each, a wave adding to the copy of its number, and the host adds the copies up (coal_vote_sums).  The flags are then set by an
 // exchange so that a tile is counted by the first cell to flag it.
-struct coal_vote_out { uint32_t *list; unsigned long long *cnt; };
+// Round 12: the list's cursor is kept in the copies as well (CVS_LIST: the length of the sub-list of that number, lcx_coal_prevote.hpp
+// coal_list_place_of; sub_cap entries of vo.list each, coal_sublist_cap) -- the one atomic of the vote that returns a value no longer queues
+// behind every other wave's.  The kept cells are the host's sum of the lengths; word CV_KEPT is no longer written.
+struct coal_vote_out { uint32_t *list; unsigned long long *cnt; uint64_t sub_cap; };
 constexpr int CV_KEPT = 0, CV_SLOTS = 64, CV_SLOT_WORDS = 16, CV_SLOT0 = 16, CV_WORDS = CV_SLOT0 + CV_SLOTS * CV_SLOT_WORDS;
-constexpr int CVS_WITH_PAIR = 0, CVS_PAIRS = 1, CVS_PAIRS_KEPT = 2, CVS_TILES_ON = 3;
+constexpr int CVS_WITH_PAIR = 0, CVS_PAIRS = 1, CVS_PAIRS_KEPT = 2, CVS_TILES_ON = 3, CVS_LIST = 4;
+static_assert(CV_SLOTS == COAL_SUBLISTS, "a sub-list per copy of the sums");
 struct coal_vote_sums { unsigned long long kept, with_pair, pairs, pairs_kept, tiles_on; };
 inline coal_vote_sums coal_vote_sums_of(const unsigned long long *h)
 {
-  coal_vote_sums v{h[CV_KEPT], 0, 0, 0, 0};
+  coal_vote_sums v{0, 0, 0, 0, 0};
   for (int i = 0; i < CV_SLOTS; ++i) {
     const unsigned long long *w = h + CV_SLOT0 + i * CV_SLOT_WORDS;
-    v.with_pair += w[CVS_WITH_PAIR]; v.pairs += w[CVS_PAIRS]; v.pairs_kept += w[CVS_PAIRS_KEPT]; v.tiles_on += w[CVS_TILES_ON];
+    v.with_pair += w[CVS_WITH_PAIR]; v.pairs += w[CVS_PAIRS]; v.pairs_kept += w[CVS_PAIRS_KEPT]; v.tiles_on += w[CVS_TILES_ON]; v.kept += w[CVS_LIST];
   }
   return v;
 }
@@ -3033,7 +3049,7 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 template <class T>
 __global__ void __launch_bounds__(BS)
 k_coal_cellvote(size_t n_cell, const uint32_t *cell_start, const uint32_t *cmax, const T *dv, const T *umin, const n_t *n_max, const T *emax, int n_emax,
-                T r_max, T dt, uint32_t *flags, uint64_t n_tiles, coal_vote_out vo = coal_vote_out{nullptr, nullptr})
+                T r_max, T dt, uint32_t *flags, uint64_t n_tiles, coal_vote_out vo = coal_vote_out{nullptr, nullptr, 0})
 {
   const size_t c = gid();
   uint32_t off = 0, end = 0;
@@ -3059,18 +3075,20 @@ k_coal_cellvote(size_t n_cell, const uint32_t *cell_start, const uint32_t *cmax,
   const unsigned long long pairs_here = has_pair ? coal_cell_pairs(off, end) : 0;
   const unsigned long long pairs = wave_sum(pairs_here), pairs_kept = wave_sum(kept ? pairs_here : 0), on = wave_sum(tiles_on);
   unsigned long long base = 0;
+  const uint64_t sub = (blockIdx.x * (BS / WAVE) + wave_id()) % CV_SLOTS;
   if (lane_id() == 0) {
-    unsigned long long *slot = vo.cnt + CV_SLOT0 + ((blockIdx.x * (BS / WAVE) + wave_id()) % CV_SLOTS) * CV_SLOT_WORDS;
+    unsigned long long *slot = vo.cnt + CV_SLOT0 + sub * CV_SLOT_WORDS;
     atomicAdd(slot + CVS_WITH_PAIR, (unsigned long long)__popcll(with_pair));
     atomicAdd(slot + CVS_PAIRS, pairs);
     if (keeps) {
-      base = atomicAdd(vo.cnt + CV_KEPT, (unsigned long long)__popcll(keeps));
+      base = atomicAdd(slot + CVS_LIST, (unsigned long long)__popcll(keeps));
       atomicAdd(slot + CVS_PAIRS_KEPT, pairs_kept);
       if (on) atomicAdd(slot + CVS_TILES_ON, on);
     }
   }
   base = __shfl(base, 0);
-  if (kept) vo.list[base + __popcll(keeps & ((1ull << lane_id()) - 1ull))] = uint32_t(c);      // (base + the wave's kept cells <= cells with a pair <= n_cell)
+  // (base + the wave's kept cells <= WAVE x the waves of this sub-list <= sub_cap)
+  if (kept) vo.list[sub * vo.sub_cap + base + __popcll(keeps & ((1ull << lane_id()) - 1ull))] = uint32_t(c);
 }
 // k_coal_cells: ONE WAVE PER LISTED CELL (round 11; EXPERIMENTS.md 7.17).  A kept tile of k_coal_ranked<.., TILES> costs a workgroup -- ids of 1 024
 // positions, keys, LDS atomics, a scan, five barriers -- to find the order of about eight cells of which usually one holds one kept pair.  Here
@@ -3087,9 +3105,9 @@ k_coal_cellvote(size_t n_cell, const uint32_t *cell_start, const uint32_t *cmax,
 // A cell above `lds_cap` droplets (the host launches the ranked path only where none is above CELLRANK_MAX; LCX_DBG2_COAL_CELL_LIST_SMALL
 // lowers the cap for the tests) is ranked window by window of CELLRANK_MAX ranks, counting in memory: correct for any size, slow.
 constexpr int COAL_CELLS_WAVES = BS / WAVE;
-constexpr uint64_t COAL_CELLS_GRID_CAP = 2048;      // workgroups at most: eight per CU of a 256-CU device at 8 KiB of LDS each
+constexpr uint64_t COAL_CELLS_GRID_CAP = 2048;      // workgroups at most: eight per CU of a 256-CU device at 9 KiB of LDS each
 struct coal_cells_args {
-  const uint32_t *list; const unsigned long long *count;       // the vote's list and its length (vo.cnt + CV_KEPT)
+  const uint32_t *list; const unsigned long long *cnt; uint64_t sub_cap;       // the vote's sub-lists, its counters (their lengths) and a sub-list's room
   const uint32_t *cmax; const n_t *n_max; int n_emax; uint32_t lds_cap;
 };
 template <class T, bool MARK, bool TALLY>
@@ -3101,16 +3119,28 @@ k_coal_cells(coal_cells_args ca, const T *emax, const uint32_t *in, const uint32
   static_assert(PER == 4, "the keys are read four at a time");
   __shared__ alignas(16) uint32_t keys_s[COAL_CELLS_WAVES][W];
   __shared__ uint32_t ids_s[COAL_CELLS_WAVES][W];
+  __shared__ uint32_t pre_s[COAL_CELLS_WAVES][COAL_SUBLISTS + 1];       // the prefix sums of the sub-lists' lengths, a copy per wave
   kc.kernel = LCX_KERNEL_HALL; rs.arr = nullptr;
   if (MARK) __builtin_assume(ijk_mark != nullptr); else ijk_mark = nullptr;
   auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
   const uint32_t lane = lane_id();
   uint32_t *keys = keys_s[wave_id()], *ids = ids_s[wave_id()];
-  const uint64_t count = *ca.count;
+  uint32_t *pre = pre_s[wave_id()];
+  {                                                   // (a lane per sub-list: COAL_SUBLISTS == WAVE)
+    static_assert(COAL_SUBLISTS == WAVE, "a lane per sub-list");
+    uint32_t incl = uint32_t(ca.cnt[CV_SLOT0 + lane * CV_SLOT_WORDS + CVS_LIST]);
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t up = __shfl_up(incl, d); if (int(lane) >= d) incl += up; }
+    pre[lane + 1] = incl;
+    if (lane == 0) pre[0] = 0u;
+    wave_sync();
+  }
+  const uint64_t count = pre[COAL_SUBLISTS];
   const T n_max = T(*ca.n_max);
   const coal_list_share sh = coal_list_share_of(blockIdx.x, gridDim.x, wave_id(), COAL_CELLS_WAVES);
   for (uint64_t li = sh.first; li < count; li += sh.step) {
-    const uint32_t c = ca.list[li];
+    const coal_list_place at = coal_list_place_of(pre, uint32_t(li));
+    const uint32_t c = ca.list[at.sub * ca.sub_cap + at.off];
     const uint32_t off = cell_start[c], end = cell_start[c + 1];
     const uint32_t n_pairs = uint32_t(coal_cell_pairs(off, end));
     if (n_pairs == 0) continue;

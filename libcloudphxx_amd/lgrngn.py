@@ -135,6 +135,8 @@ class dbg2(enum.IntFlag):
     NO_COAL_CELL_LIST = 1 << 4
     COAL_CELL_LIST_ALWAYS = 1 << 5
     COAL_CELL_LIST_SMALL = 1 << 6
+    NO_COAL_CMAX_FLOOR = 1 << 7
+    COAL_CMAX_FLOOR_HIGH = 1 << 8
 
 
 class cond_kernel(enum.IntEnum):
