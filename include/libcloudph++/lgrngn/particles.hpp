@@ -22,6 +22,7 @@
 #include "../../lcx_move_rates.h"
 #include "../../lcx_track.h"
 #include "../../lcx_track_budget.h"
+#include "../../lcx_dump.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -134,6 +135,16 @@ namespace libcloudphxx { namespace lgrngn {
     std::vector<double> rec, time;
     std::vector<unsigned long long> steps;
     double at(size_t s, track_field_t f, size_t k) const { return rec[(s * size_t(LCX_TRK_FIELDS) + size_t(f)) * n_tracked + k]; }
+  };
+  // the fields of particles_t<real_t, HIP>::dump (an extension as well; include/lcx_dump.h defines each): the twelve of a track record, then
+  // the storage slot, the track mark, the in-cloud time and the eight chemical masses
+  enum dump_field_t
+  {
+    dmp_n = LCX_DMP_N, dmp_x = LCX_DMP_X, dmp_y = LCX_DMP_Y, dmp_z = LCX_DMP_Z, dmp_rw2 = LCX_DMP_RW2, dmp_rd3 = LCX_DMP_RD3,
+    dmp_kappa = LCX_DMP_KAPPA, dmp_vt = LCX_DMP_VT, dmp_cell = LCX_DMP_CELL, dmp_T = LCX_DMP_T, dmp_RH = LCX_DMP_RH, dmp_rv = LCX_DMP_RV,
+    dmp_slot = LCX_DMP_SLOT, dmp_track = LCX_DMP_TRACK, dmp_incloud_time = LCX_DMP_INCLOUD_TIME, dmp_chem_HNO3 = LCX_DMP_CHEM_HNO3,
+    dmp_chem_NH3 = LCX_DMP_CHEM_NH3, dmp_chem_CO2 = LCX_DMP_CHEM_CO2, dmp_chem_SO2 = LCX_DMP_CHEM_SO2, dmp_chem_H2O2 = LCX_DMP_CHEM_H2O2,
+    dmp_chem_O3 = LCX_DMP_CHEM_O3, dmp_chem_S_VI = LCX_DMP_CHEM_S_VI, dmp_chem_H = LCX_DMP_CHEM_H, dmp_fields = LCX_DMP_FIELDS
   };
   // the accumulators of particles_t<real_t, HIP>::track_budget (an extension as well; include/lcx_track_budget.h defines each)
   enum track_budget_field_t
@@ -526,6 +537,29 @@ namespace libcloudphxx { namespace lgrngn {
       size_t got = 0;
       detail::lcx_check(lcx_track_budget_read(pimpl->h, out.rows.data(), size_t(LCX_TRB_FIELDS) * out.n_tracked, out.n_tracked, out.n_samples, &got,
                                               out.acc.data(), out.n_tracked, 0));
+    }
+    // EXTENSION (include/lcx_dump.h): the chosen fields of every droplet that satisfies every clause of `sel` (as track_select reads it) and
+    // lies in box, in storage order and as doubles: one vector per field, each of n_written elements.  max_count == 0: everything (the call
+    // counts first); otherwise at most max_count droplets, every stride-th of the n_qualifying.  The object is only read.
+    std::vector<std::vector<double>> dump(const diag_req_t<real_t> &sel, const std::vector<double> &box, const std::vector<dump_field_t> &fields,
+                                          size_t max_count = 0, size_t *n_qualifying = nullptr, unsigned long long *stride = nullptr)
+    {
+      std::vector<lcx_diag_clause_t> c;
+      for (const auto &cl : sel.clauses) c.push_back(lcx_diag_clause_t{cl.sel, double(cl.lo), double(cl.hi)});
+      if (!box.empty() && box.size() != 6) throw std::runtime_error("libcloudph++: dump: box must hold six bounds (x0, x1, y0, y1, z0, z1)");
+      const double *b = box.empty() ? nullptr : box.data();
+      std::vector<int> f(fields.begin(), fields.end());
+      size_t Q = 0, written = 0;
+      if (max_count == 0) {
+        detail::lcx_check(lcx_dump(pimpl->h, c.data(), int(c.size()), b, f.data(), int(f.size()), nullptr, 0, 0, 0, &Q, nullptr, nullptr));
+        max_count = std::max<size_t>(Q, 1);
+      }
+      std::vector<double> flat(f.size() * max_count);
+      detail::lcx_check(lcx_dump(pimpl->h, c.data(), int(c.size()), b, f.data(), int(f.size()), flat.data(), max_count, max_count, 0, &Q, &written, stride));
+      if (n_qualifying) *n_qualifying = Q;
+      std::vector<std::vector<double>> out(f.size());
+      for (size_t k = 0; k < f.size(); ++k) out[k].assign(flat.begin() + k * max_count, flat.begin() + k * max_count + written);
+      return out;
     }
 
   private:

@@ -33,6 +33,7 @@
 #include "../../include/lcx_move_rates.h"
 #include "../../include/lcx_track.h"
 #include "../../include/lcx_track_budget.h"
+#include "../../include/lcx_dump.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -175,6 +176,8 @@ struct IParticles {
   virtual void track_budget_disable() { not_built("track"); }
   virtual void track_budget_info(int *, unsigned long long *, unsigned long long *, unsigned long long *) { not_built("track"); }
   virtual void track_budget_read(double *, size_t, size_t, size_t, size_t *, double *, size_t, bool) { not_built("track"); }
+  // the particle dump (include/lcx_dump.h)
+  virtual void dump(const lcx_diag_clause_t *, int, const double *, const int *, int, double *, size_t, size_t, bool, size_t *, size_t *, unsigned long long *) { not_built("dump"); }
   virtual void get_state_u64(const char *name, unsigned long long *out, size_t cap, size_t *n) = 0;
   virtual void get_state_real(const char *name, double *out, size_t cap, size_t *n) = 0;
   virtual void set_particles(size_t n, const unsigned long long *mult, const double *rd3, const double *rw2, const double *kpa,
@@ -2208,6 +2211,80 @@ struct Particles : IParticles {
     for (size_t s = 0; s < trk_ns; ++s) { if (steps) steps[s] = trk_steps[s]; if (time) time[s] = trk_times[s]; }
     if (n_samples) *n_samples = trk_ns;
     if (reset) { trk_ns = 0; trk_dropped = 0; }   // (the budget's rows are counted by trk_ns as well: emptied with the samples)
+  }
+  // ---- the particle dump (include/lcx_dump.h): a bit per storage slot, a count per tile, one gather; the object is only read ----
+  // No ensure_compact, no sid(): the storage is taken as it stands, dead slots and an owed sort included.  dmp_mask and dmp_part are
+  // scratch of the object, grown on demand as trk_part is; the staging buffer of a host dump lives for the call.
+  DevBuf<unsigned long long> dmp_mask; DevBuf<uint32_t> dmp_part, dmp_total;
+  void dump(const lcx_diag_clause_t *clause, int n_clauses, const double *box, const int *field, int n_fields, double *out, size_t field_stride, size_t max_count,
+            bool on_device, size_t *n_qualifying, size_t *n_written, unsigned long long *stride_out) override
+  {
+    if (!init_called) throw lcx_error("libcloudph++: dump: called before init()");
+    const bool pair[3] = {o.nx != 0, o.ny != 0, o.nz != 0};
+    std::string err;
+    if (!dump::validate(clause, n_clauses, box, field, n_fields, err, pair, ix_chem >= 0, ix_ict >= 0)) throw lcx_error(err);
+    if (!dump::validate_out(out, field_stride, max_count, err)) throw lcx_error(err);
+    if (n_qualifying) *n_qualifying = 0;
+    if (n_written) *n_written = 0;
+    if (stride_out) *stride_out = 0;
+    if (!nphys) { sync(); return; }
+    Range r(this, "dump");
+    dump_sel_arg<T> a{A.n.p, A.rd3.p, A.rw2.p, A.kpa.p, A.x.p, A.y.p, A.z.p, n_clauses, {}, {}, {}, box ? 1 : 0, {0, 0, 0, 0, 0, 0}};
+    for (int c = 0; c < n_clauses; ++c) {
+      double lo = 0, hi = 0;
+      a.sel[c] = clause[c].sel;
+      if (diag::sel_is_range(clause[c].sel)) diag::rng_bounds(clause[c].sel, clause[c].lo, clause[c].hi, lo, hi);
+      a.lo[c] = T(lo); a.hi[c] = T(hi);
+    }
+    if (box) for (int d = 0; d < 3; ++d) if (pair[d]) { a.box[2 * d] = box[2 * d]; a.box[2 * d + 1] = box[2 * d + 1]; }
+    const size_t tiles = (nphys + SCAN_TILE - 1) / SCAN_TILE;
+    dmp_mask.alloc(tiles * size_t(DUMP_TILE_WORDS)); dmp_part.alloc(tiles); dmp_total.alloc(1);
+    hipLaunchKernelGGL(k_dump_mark<T>, dim3(unsigned(tiles)), dim3(BS), 0, st, nphys, a, dmp_mask.p, dmp_part.p);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, dmp_part.p, tiles, dmp_total.p);
+    uint32_t Q = 0;
+    read_back(&Q, dmp_total.p, 1);                   // (the one small read-back: the stride and the staging buffer's size come from it)
+    if (n_qualifying) *n_qualifying = Q;
+    if (!out) return;
+    const uint64_t stride = track::stride(Q, max_count);
+    if (!stride) return;
+    const size_t took = size_t(track::count(Q, stride));
+    dump_gather_arg g{n_fields, {}, ijk.p, ncell};
+    for (int f = 0; f < n_fields; ++f) {
+      const int id = field[f];
+      auto real = [&](const T *p) { return dump::field_desc{p ? dump::K_REAL : dump::K_ZERO, p}; };
+      auto cell = [&](const T *p) { return dump::field_desc{dump::K_CELL, p}; };
+      dump::field_desc d{dump::K_ZERO, nullptr};
+      switch (id) {
+        case LCX_DMP_N: d = {dump::K_U64, A.n.p}; break;
+        case LCX_DMP_X: d = real(A.x.p); break;
+        case LCX_DMP_Y: d = real(A.y.p); break;
+        case LCX_DMP_Z: d = real(A.z.p); break;
+        case LCX_DMP_RW2: d = real(A.rw2.p); break;
+        case LCX_DMP_RD3: d = real(A.rd3.p); break;
+        case LCX_DMP_KAPPA: d = real(A.kpa.p); break;
+        case LCX_DMP_VT: d = real(A.vt.p); break;
+        case LCX_DMP_CELL: d = {dump::K_IJK, nullptr}; break;
+        case LCX_DMP_T: d = cell(Tk.p); break;
+        case LCX_DMP_RH: d = cell(RH.p); break;
+        case LCX_DMP_RV: d = cell(rv.p); break;
+        case LCX_DMP_SLOT: d = {dump::K_SLOT, nullptr}; break;
+        case LCX_DMP_TRACK: d = real(ix_trk >= 0 ? A.ext[ix_trk].p : nullptr); break;
+        case LCX_DMP_INCLOUD_TIME: d = real(A.ext[ix_ict].p); break;
+        default: d = real(A.ext[ix_chem + (id - LCX_DMP_CHEM_HNO3)].p); break;        // (validated: one of the eight masses)
+      }
+      g.f[f] = d;
+    }
+    if (on_device) {
+      hipLaunchKernelGGL(k_dump_gather<T>, dim3(unsigned(tiles)), dim3(BS), 0, st, nphys, (const unsigned long long *)dmp_mask.p, (const uint32_t *)dmp_part.p, uint32_t(stride), g, out, field_stride);
+      sync();
+    } else {
+      DevBuf<double> stage; stage.alloc(size_t(n_fields) * took);
+      hipLaunchKernelGGL(k_dump_gather<T>, dim3(unsigned(tiles)), dim3(BS), 0, st, nphys, (const unsigned long long *)dmp_mask.p, (const uint32_t *)dmp_part.p, uint32_t(stride), g, stage.p, took);
+      HIPCHK(hipMemcpy2DAsync(out, field_stride * sizeof(double), stage.p, took * sizeof(double), took * sizeof(double), size_t(n_fields), hipMemcpyDeviceToHost, st));
+      sync();                                        // (`stage` is read by the copy until here)
+    }
+    if (n_written) *n_written = took;
+    if (stride_out) *stride_out = stride;
   }
   // ---- the budget of tracked droplets (include/lcx_track_budget.h): seven accumulators per track index, fed by passes of their own ----
   // trb_begin ahead of a pass stores n, rw2, rd3 of every index (per index, so no permutation can invalidate them); trb_end behind it adds
@@ -4784,6 +4861,17 @@ int lcx_track_info(lcx_particles *h, int *enabled, size_t *max_tracked, size_t *
 int lcx_track_read(lcx_particles *h, double *out, size_t sample_stride, size_t field_stride, unsigned long long *steps, double *time, size_t cap_samples,
                    size_t *n_samples, int out_on_device, int reset)
 { LCX_TRY(H->track_read(out, sample_stride, field_stride, steps, time, cap_samples, n_samples, out_on_device != 0, reset != 0)) }
+// ---- the particle dump (include/lcx_dump.h) ----
+int lcx_dump_check(const lcx_diag_clause_t *clause, int n_clauses, const double *box, const int *field, int n_fields)
+{
+  std::string err;                                   // (host only: no device is looked for or bound)
+  if (lcx::dump::validate(clause, n_clauses, box, field, n_fields, err)) return 0;
+  g_err = err;
+  return 1;
+}
+int lcx_dump(lcx_particles *h, const lcx_diag_clause_t *clause, int n_clauses, const double *box, const int *field, int n_fields, double *out, size_t field_stride,
+             size_t max_count, int out_on_device, size_t *n_qualifying, size_t *n_written, unsigned long long *stride)
+{ LCX_TRY(H->dump(clause, n_clauses, box, field, n_fields, out, field_stride, max_count, out_on_device != 0, n_qualifying, n_written, stride)) }
 // ---- their budget (include/lcx_track_budget.h) ----
 int lcx_track_budget_enable(lcx_particles *h) { LCX_TRY(H->track_budget_enable()) }
 int lcx_track_budget_disable(lcx_particles *h) { LCX_TRY(H->track_budget_disable()) }

@@ -15,6 +15,7 @@
 #include "lcx_diag_plan.hpp"
 #include "lcx_coal_prevote.hpp"
 #include "lcx_track_plan.hpp"
+#include "lcx_dump_plan.hpp"
 
 namespace lcx {
 
@@ -5240,6 +5241,132 @@ __global__ void k_track_budget_read(const double *src, size_t n_samples, size_t 
   const size_t i = gid(); if (i >= n_samples * per) return;
   const size_t s = i / per, f = (i - s * per) / n_tracked, k = (i - s * per) % n_tracked;
   out[s * sample_stride + f * field_stride + k] = src[(s * size_t(LCX_TRB_FIELDS) + f) * max_tracked + k];
+}
+
+// ============================================================================================
+// the particle dump (include/lcx_dump.h; its descriptors: lcx_dump_plan.hpp; its integer rule: lcx_track_plan.hpp)
+// ============================================================================================
+// A stream compaction over the whole storage in two passes.  k_dump_mark is the only one that reads the predicate's columns: a bit per
+// slot (a wave's ballot is one word of the mask, word w = slots [64 w, 64 w + 64)) and a count per tile of SCAN_TILE slots; k_scan_sums
+// turns the counts into offsets; k_dump_gather reads the bits back, ranks every set one and moves the fields of the ranks that the
+// stride rule takes.  Both read only: no column, no counter of the object changes.
+// The predicate is track_qualifies without the mark (a tracked droplet qualifies): the same clauses through nfilt_step, the same box.
+template <class T> struct dump_sel_arg {
+  const n_t *n; const T *rd3, *rw2, *kpa, *x, *y, *z;               // x, y, z: nullptr for a dimension the object lacks
+  int n_clauses, sel[LCX_DIAG_MAX_CLAUSES]; T lo[LCX_DIAG_MAX_CLAUSES], hi[LCX_DIAG_MAX_CLAUSES];
+  int has_box; double box[6];
+};
+template <class T> __device__ __forceinline__ bool dump_qualifies(const dump_sel_arg<T> &a, size_t i)
+{
+  if (a.n[i] == 0) return false;
+  T y = T(1);
+  for (int cl = 0; cl < a.n_clauses; ++cl) {
+    const int sel = a.sel[cl];
+    if (sel == LCX_DIAG_SEL_ALL) continue;
+    const T v = sel == LCX_DIAG_SEL_DRY ? a.rd3[i] : sel == LCX_DIAG_SEL_KAPPA ? a.kpa[i] : a.rw2[i];
+    y = nfilt_step(sel == LCX_DIAG_SEL_WATER ? 2 : 1, y, v, a.lo[cl], a.hi[cl]);
+  }
+  if (!(y > T(0))) return false;
+  if (a.has_box) {
+    if (a.x) { const double p = double(a.x[i]); if (!(p >= a.box[0] && p < a.box[1])) return false; }
+    if (a.y) { const double p = double(a.y[i]); if (!(p >= a.box[2] && p < a.box[3])) return false; }
+    if (a.z) { const double p = double(a.z[i]); if (!(p >= a.box[4] && p < a.box[5])) return false; }
+  }
+  return true;
+}
+constexpr int DUMP_TILE_WORDS = SCAN_TILE / WAVE;                    // 32 mask words per tile
+// mask: (n_storage + 63) / 64 words are written, those of waves that hold a slot; partial: one count per tile
+template <class T>
+__global__ void __launch_bounds__(BS) k_dump_mark(size_t n_storage, dump_sel_arg<T> a, unsigned long long *mask, uint32_t *partial)
+{
+  __shared__ uint32_t lds[BS / WAVE];
+  const size_t base = size_t(blockIdx.x) * SCAN_TILE;
+  uint32_t cnt = 0;
+  for (int it = 0; it < SCAN_TILE / BS; ++it) {
+    const size_t i = base + size_t(it) * BS + threadIdx.x;
+    const bool q = i < n_storage && dump_qualifies(a, i);
+    const unsigned long long bal = __ballot(q);
+    if (lane_id() == 0 && i < n_storage) mask[i / WAVE] = bal;      // (lane 0's slot is the word's first: i / WAVE < the words held)
+    cnt += uint32_t(__popcll(bal));
+  }
+  if (lane_id() == 0) lds[wave_id()] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) { uint32_t s = 0; for (int w = 0; w < BS / WAVE; ++w) s += lds[w]; partial[blockIdx.x] = s; }
+}
+// The fields of one dump: a source per field (dump::kind_t), at most LCX_DMP_FIELDS, in the argument block
+struct dump_gather_arg {
+  int n_fields; dump::field_desc f[LCX_DMP_FIELDS];
+  const uint32_t *ijk; size_t n_cell;
+};
+// The tile's 32 words are read once, by the first 32 lanes, and kept in LDS with their running popcounts; then every wave takes the words
+// of its slots (word it * 4 + wave: the slots of k_dump_mark's iteration `it`); a word that is 0 costs it nothing more.  The rank of a set
+// bit: the tile's offset + the popcounts of the tile's lower words + the popcount of the word's lower bits.  A taken rank q is written at
+// q / stride: out[f * field_stride + q / stride] < out[f * field_stride + n_written], n_written <= field_stride (the host has checked).
+// Field by field, the lane's (up to) eight values are loaded before the first is stored: eight loads in flight instead of a chain of
+// load, wait, store per field and slot (that chain made a strided dump of 1.3e8 droplets latency-bound, EXPERIMENTS.md 7.22).
+constexpr int DUMP_ITERS = SCAN_TILE / BS;
+constexpr uint32_t DUMP_NOT_TAKEN = 0xFFFFFFFFu;                     // (an index: below n_written <= Q < 2^32 - 1 slots)
+template <class T, int KIND>
+__device__ __forceinline__ void dump_move(const void *p, const uint32_t *ijk, size_t n_cell, size_t first, const uint32_t (&at)[DUMP_ITERS], double *row)
+{
+  double v[DUMP_ITERS];
+#pragma unroll
+  for (int it = 0; it < DUMP_ITERS; ++it) {
+    v[it] = 0.;
+    if (at[it] == DUMP_NOT_TAKEN) continue;
+    const size_t i = first + size_t(it) * BS;
+    if (KIND == dump::K_U64) v[it] = double(static_cast<const n_t *>(p)[i]);
+    else if (KIND == dump::K_IJK) v[it] = double(ijk[i]);
+    else if (KIND == dump::K_SLOT) v[it] = double(i);
+    else if (KIND == dump::K_REAL) v[it] = double(static_cast<const T *>(p)[i]);
+    else if (KIND == dump::K_CELL) { const uint32_t c = ijk[i]; v[it] = c < n_cell ? double(static_cast<const T *>(p)[c]) : __builtin_nan(""); }
+  }
+#pragma unroll
+  for (int it = 0; it < DUMP_ITERS; ++it) if (at[it] != DUMP_NOT_TAKEN) row[at[it]] = v[it];
+}
+template <class T>
+__global__ void __launch_bounds__(BS)
+k_dump_gather(size_t n_storage, const unsigned long long *mask, const uint32_t *tile_offs, uint32_t stride, dump_gather_arg g, double *out, size_t field_stride)
+{
+  __shared__ unsigned long long words[DUMP_TILE_WORDS];
+  __shared__ uint32_t below[DUMP_TILE_WORDS];
+  const size_t base = size_t(blockIdx.x) * SCAN_TILE;
+  if (threadIdx.x < WAVE) {                                          // (the whole first wave: the scan is the wave's)
+    const size_t first = base + size_t(threadIdx.x) * WAVE;          // the word's first slot
+    const unsigned long long w = threadIdx.x < DUMP_TILE_WORDS && first < n_storage ? mask[first / WAVE] : 0ull;
+    const uint32_t c = uint32_t(__popcll(w));
+    const uint32_t inc = wave_inclusive_scan(c);
+    if (threadIdx.x < DUMP_TILE_WORDS) { words[threadIdx.x] = w; below[threadIdx.x] = inc - c; }
+  }
+  __syncthreads();
+  // (ranks and stride are below 2^32, as the u32 counts of k_scan_sums are: widened from 32 bits, the rule's division is a 32-bit one)
+  const uint32_t run = tile_offs[blockIdx.x];
+  uint32_t at[DUMP_ITERS];
+  bool any = false;
+#pragma unroll
+  for (int it = 0; it < DUMP_ITERS; ++it) {
+    const unsigned wi = unsigned(it) * (BS / WAVE) + wave_id();
+    const unsigned long long w = words[wi];
+    at[it] = DUMP_NOT_TAKEN;
+    if (!((w >> lane_id()) & 1ull)) continue;                        // (a set bit: its slot is below n_storage)
+    const uint32_t q = run + below[wi] + uint32_t(__popcll(w & ((1ull << lane_id()) - 1ull)));
+    if (!track::taken(q, stride)) continue;
+    at[it] = q / stride; any = true;
+  }
+  if (!__ballot(any)) return;                                        // (a wave none of whose slots is taken: the words and nothing else)
+  const size_t first = base + threadIdx.x;
+  for (int f = 0; f < g.n_fields; ++f) {
+    const void *p = g.f[f].p;
+    double *row = out + size_t(f) * field_stride;
+    switch (g.f[f].kind) {
+      case dump::K_U64: dump_move<T, dump::K_U64>(p, g.ijk, g.n_cell, first, at, row); break;
+      case dump::K_IJK: dump_move<T, dump::K_IJK>(p, g.ijk, g.n_cell, first, at, row); break;
+      case dump::K_SLOT: dump_move<T, dump::K_SLOT>(p, g.ijk, g.n_cell, first, at, row); break;
+      case dump::K_REAL: dump_move<T, dump::K_REAL>(p, g.ijk, g.n_cell, first, at, row); break;
+      case dump::K_CELL: dump_move<T, dump::K_CELL>(p, g.ijk, g.n_cell, first, at, row); break;
+      default: dump_move<T, dump::K_ZERO>(p, g.ijk, g.n_cell, first, at, row); break;
+    }
+  }
 }
 
 } // namespace lcx

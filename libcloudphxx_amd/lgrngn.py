@@ -504,6 +504,54 @@ def track_budget_check_out(out, n_samples, n_tracked):
         raise ValueError("libcloudph++: track budget: out must have unit stride along the droplets")
 
 
+# ---- the particle dump (include/lcx_dump.h)
+DUMP_FIELDS = TRACK_FIELDS + ("slot", "track", "incloud_time", "chem_hno3", "chem_nh3", "chem_co2", "chem_so2", "chem_h2o2", "chem_o3",
+                              "chem_s_vi", "chem_h")                 # enum LCX_DMP_*, in its order: the twelve of a track record as
+DUMP_DEFAULT_FIELDS = ("n", "x", "y", "z", "rw2", "rd3", "kappa")   # TRACK_FIELDS spells them, the others in lower case
+_DUMP_INDEX = {f.lower(): i for i, f in enumerate(DUMP_FIELDS)}
+
+
+def dump_fields(fields):
+    """names of DUMP_FIELDS (any letter case), each at most once, as (array of int, n, the names as DUMP_FIELDS spells them) for lcx_dump"""
+    if isinstance(fields, str):
+        fields = (fields,)
+    low = [str(f).lower() for f in fields]
+    if not 1 <= len(low) <= len(DUMP_FIELDS):
+        raise ValueError("libcloudph++: dump: n_fields = %d is outside 1 .. %d" % (len(low), len(DUMP_FIELDS)))
+    for nm in low:
+        if nm not in _DUMP_INDEX:
+            raise ValueError("libcloudph++: dump: unknown field %r (one of %s)" % (nm, ", ".join(DUMP_FIELDS)))
+        if low.count(nm) > 1:
+            raise ValueError("libcloudph++: dump: field %r is given twice" % nm)
+    ids = [_DUMP_INDEX[nm] for nm in low]
+    return (C.c_int * len(ids))(*ids), len(ids), [DUMP_FIELDS[i] for i in ids]
+
+
+def dump_check_out(out, n_fields, max_count):
+    """refuses an `out` of dump that is no DeviceArray of (n_fields, max_count) doubles with unit stride along the droplets"""
+    if out is None:
+        return
+    if not isinstance(out, DeviceArray) or len(out.shape) != 2 or tuple(out.shape) != (n_fields, max_count):
+        raise ValueError("libcloudph++: dump: out must be a DeviceArray of shape (n_fields, max_count) = (%d, %d)" % (n_fields, max_count))
+    if max_count > 1 and out.strides[1] != 1:
+        raise ValueError("libcloudph++: dump: out must have unit stride along the droplets")
+    if n_fields > 1 and out.strides[0] < max_count:
+        raise ValueError("libcloudph++: dump: out's row stride is below max_count")
+
+
+def dump_check(clauses=(("all",),), box=None, fields=DUMP_DEFAULT_FIELDS, lib=None):
+    """lcx_dump_check on clauses in diag_batch's notation, a box of six numbers and field names or numbers; needs no GPU.  Raises the
+    library's text."""
+    lib = lib if lib is not None else _lib.load()
+    arr, n = track_clauses(clauses)
+    b = None if box is None else (C.c_double * 6)(*[float(v) for v in box])
+    ids = [_DUMP_INDEX[f.lower()] if isinstance(f, str) else int(f) for f in fields]
+    fa = (C.c_int * max(len(ids), 1))(*ids)
+    if lib.lcx_dump_check(arr, C.c_int(n), b, fa, C.c_int(len(ids))) != 0:
+        lib.lcx_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.lcx_last_error().decode())
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -1211,6 +1259,48 @@ class particles_t:
         if out is None:
             for f, nm in enumerate(TRACK_BUDGET_FIELDS):
                 res[nm] = arr[:ns, f, :nt].copy()
+        return res
+
+    # -- the particle dump (include/lcx_dump.h; no reference counterpart)
+    def _dump_call(self, arr, n, b, fa, nf, ptr, field_stride, max_count, on_device):
+        q, w, st = C.c_size_t(), C.c_size_t(), C.c_ulonglong()
+        self._chk(self._f("dump")(self._h, arr, C.c_int(n), b, fa, C.c_int(nf), C.c_void_p(ptr), C.c_size_t(field_stride), C.c_size_t(max_count),
+                                  C.c_int(int(on_device)), C.byref(q), C.byref(w), C.byref(st)))
+        return q.value, w.value, st.value
+
+    def dump_count(self, clauses=(("all",),), box=None):
+        """Q: how many droplets satisfy every clause (see track_clauses) and lie in box (x0, x1, y0, y1, z0, z1); nothing is written"""
+        arr, n = track_clauses(clauses)
+        fa = (C.c_int * 1)(0)
+        return self._dump_call(arr, n, track_box(box), fa, 1, None, 0, 0, False)[0]
+
+    def dump(self, clauses=(("all",),), box=None, fields=DUMP_DEFAULT_FIELDS, max_count=None, out=None):
+        """the chosen fields (names of DUMP_FIELDS) of every qualifying droplet, in storage order: a dict {field: float64 array of n_written}
+        plus "n_qualifying" and "stride" (ints).  max_count=None: count first, then everything; otherwise at most max_count droplets, every
+        stride-th of the qualifying ones.  With out= (a DeviceArray of the object's device, (len(fields), max_count) doubles with unit
+        stride along the droplets) the values go there, row f holding fields[f], and the dict holds the counts and "n_written" only.
+        The object is only read: nothing is compacted, sorted or drawn."""
+        arr, n = track_clauses(clauses)
+        b = track_box(box)
+        fa, nf, names = dump_fields(fields)
+        if out is not None:
+            if max_count is None:
+                max_count = out.shape[1] if isinstance(out, DeviceArray) and len(out.shape) == 2 else 0
+            max_count = int(max_count)
+            if max_count < 1:
+                raise ValueError("libcloudph++: dump: max_count must be at least 1")
+            dump_check_out(out, nf, max_count)
+            Q, w, st = self._dump_call(arr, n, b, fa, nf, out.ptr, out.strides[0] if nf > 1 else max(out.strides[0], max_count), max_count, True)
+            return {"n_qualifying": Q, "stride": st, "n_written": w}
+        if max_count is None:
+            max_count = max(self._dump_call(arr, n, b, fa, nf, None, 0, 0, False)[0], 1)
+        max_count = int(max_count)
+        if max_count < 1:
+            raise ValueError("libcloudph++: dump: max_count must be at least 1")
+        host = np.zeros((nf, max_count), dtype=np.float64)
+        Q, w, st = self._dump_call(arr, n, b, fa, nf, host.ctypes.data, max_count, max_count, False)
+        res = {nm: host[f, :w].copy() for f, nm in enumerate(names)}
+        res["n_qualifying"], res["stride"] = Q, st
         return res
 
     def outbuf(self):
