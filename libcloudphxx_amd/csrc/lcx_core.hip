@@ -38,6 +38,7 @@
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
 #include "lcx_coal_floor_probe.h"
+#include "lcx_coal_plan.hpp"
 
 // every kernel launch of this translation unit and every host wait for a stream are COUNTED (lcx_get_state_u64 "raw_launches"): what a
 // step costs a thin slab or a 2-D set-up is its launches and its waits, not its bytes (bench.py's c2 leg reports both per step)
@@ -54,6 +55,10 @@ struct lcx_error : std::runtime_error { using std::runtime_error::runtime_error;
   throw lcx_error(std::string("libcloudph++ (HIP): ") + hipGetErrorString(e_) + " at " #expr); } while (0)
 
 static inline unsigned nblk(size_t n, unsigned bs = BS) { return unsigned((n + bs - 1) / bs); }
+// run-time bools as std::bool_constants, for a generic lambda that names a kernel's instantiation by them: with_bool(b, [&](auto B) {
+// launch(k<decltype(B)::value>); }) -- for the launches that exist in the full product of their flags, and for no others
+template <class F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static inline void with_bool(bool a, bool b, F &&f) { with_bool(a, [&](auto A) { with_bool(b, [&](auto B) { f(A, B); }); }); }
 
 template <class T> struct DevBuf {
   T *p = nullptr; size_t n = 0;
@@ -443,81 +448,71 @@ struct Particles : IParticles {
   DevBuf<unsigned long long> coal_skip_cnt;  // LCX_DBG2_COAL_SKIP_COUNT: {pairs skipped, pairs examined, workgroups that left before ranking, workgroups
                                              // launched} of the last step_async ("raw_coal_skip", "raw_coal_wg")
   unsigned long long coal_wg_no_exit = 0;    // (workgroups of its bound launches without the early exit, LCX_DBG2_NO_COAL_RANK_EXIT: that kernel counts none)
-  // the bound pays only where it skips: a sample of the launch's counters comes back to the host without a wait (a copy and an event, polled by
-  // the next step_async); below COAL_SKIP_MIN_SHARE^-1 of the pairs skipped, COAL_SKIP_PAUSE steps run without maxima and without bound, then
-  // one step probes again.  Results do not depend on it: a launch with the bound and one without give the same bits.
-  static constexpr int COAL_SKIP_PAUSE = 32; static constexpr unsigned long long COAL_SKIP_MIN_SHARE = 200;      // (0.5 %)
-  // Likewise the workgroups' exit ahead of the ranking (k_coal_ranked<.., SKIP, EXIT>): a workgroup that ranks after all pays for the vote and
-  // for id loads one level later -- +0.17 ms on a launch of the 128^3 x 64 box in which none leaves, against -0.53 ms where all do, so the exit
-  // breaks even at 0.17 / (0.17 + 0.53) = 0.24 of the workgroups leaving (EXPERIMENTS.md 7.10).  Below COAL_EXIT_MIN_PERCENT of them in a
-  // launch's counters (or the sample of them) the next COAL_EXIT_PAUSE bound launches take round 8's form, then one probes again.  The same
-  // bits either way.  (Which launch the flags are handed to, the tiles' or the kept cells': COAL_CELLS_MAX_PERCENT, with its figures, below.)
-  static constexpr int COAL_EXIT_PAUSE = 32; static constexpr unsigned long long COAL_EXIT_MIN_PERCENT = 24;
-  int exit_pause = 0;
+  // ---- the adaptive choices of its launch (lcx_coal_plan.hpp: the form, the two pause rules; round 8-11) ----
+  coal_adapt adapt;                          // the pauses of the bound and of the exit, the last polled vote
+  coal_toggles coal_tg() const
+  {
+    return coal_toggles{dbg2(LCX_DBG2_COAL_SKIP_COUNT), dbg2(LCX_DBG2_NO_COAL_RANK_EXIT), dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS), dbg2(LCX_DBG2_NO_COAL_PREVOTE),
+                        dbg2(LCX_DBG2_NO_COAL_CELL_LIST), dbg2(LCX_DBG2_COAL_CELL_LIST_ALWAYS)};
+  }
   int last_coal_exit = 0;                    // ("raw_coal_exit": the coalescence launches of the last step_async in the EXIT form)
-  DevBuf<unsigned long long> coal_skip_sample; void *skip_pinned = nullptr; hipEvent_t ev_skip = nullptr;
-  bool skip_sample_pending = false; int skip_sample_n = 0, skip_pause = 0;
+  // a few counters on their way to the host without a wait: a pinned copy and an event behind the launch, polled by the next step_async
+  struct HostSample {
+    unsigned long long *pinned = nullptr; hipEvent_t ev = nullptr; bool pending = false; size_t n = 0;
+    void send(const unsigned long long *src, size_t n_words, size_t room, hipStream_t s)
+    {
+      if (!pinned) { HIPCHK(hipHostMalloc((void **)&pinned, room * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
+      n = n_words;
+      HIPCHK(hipMemcpyAsync(pinned, src, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipEventRecord(ev, s));
+      pending = true;
+    }
+    const unsigned long long *arrived()      // the words, once, when the copy has landed
+    {
+      if (!pending || hipEventQuery(ev) != hipSuccess) return nullptr;
+      pending = false;
+      return pinned;
+    }
+    void release() { if (pinned) (void)hipHostFree(pinned); if (ev) (void)hipEventDestroy(ev); }
+  };
+  DevBuf<unsigned long long> coal_skip_sample; HostSample skip_sample;
   void poll_skip_sample()
   {
-    if (!skip_sample_pending || hipEventQuery(ev_skip) != hipSuccess) return;
-    skip_sample_pending = false;
-    const unsigned long long *h = static_cast<const unsigned long long *>(skip_pinned);
-    unsigned long long skipped = 0, examined = 0;
-    const int n_pairs = skip_sample_n / 2;                                                       // (behind the pairs' counters: the workgroups')
-    for (int i = 0; i < n_pairs; i += 2) { skipped += h[i]; examined += h[i + 1]; }
-    if (examined && skipped * COAL_SKIP_MIN_SHARE < examined) skip_pause = COAL_SKIP_PAUSE;
-    unsigned long long left = 0, launched = 0;
-    for (int i = n_pairs; i < skip_sample_n; i += 2) { left += h[i]; launched += h[i + 1]; }
-    if (launched && left * 100 < launched * COAL_EXIT_MIN_PERCENT) exit_pause = COAL_EXIT_PAUSE;          // (a launch in round 8's form counts no workgroups)
+    const unsigned long long *h = skip_sample.arrived();
+    if (!h) return;
+    unsigned long long skipped = 0, examined = 0, left = 0, launched = 0;
+    const size_t n_pairs = skip_sample.n / 2;                                                    // (behind the pairs' counters: the workgroups')
+    for (size_t i = 0; i < n_pairs; i += 2) { skipped += h[i]; examined += h[i + 1]; }
+    for (size_t i = n_pairs; i < skip_sample.n; i += 2) { left += h[i]; launched += h[i + 1]; }
+    adapt.feed(skipped, examined, left, launched);
   }
   // ---- the cells' vote ahead of the EXIT launch (round 10; lcx_coal_prevote.hpp, k_coal_umin, k_coal_cellvote) ----
   // step_async launches k_coal_umin on the side stream beside the velocity pass, for the call number that coal() will hand to rand_u01; coal() makes
   // `st` wait for it, lets the cells vote and hands the tiles' flags to the kernel -- if the draws were made for exactly the call, seed and cells that
-  // the launch is about to use (pv_*_of), else the launch is round 9's and pv_fallback counts it.  Results cannot depend on it: the same bits.
+  // the launch is about to use (pv.of), else the launch is round 9's and pv.fallback counts it.  Results cannot depend on it: the same bits.
   DevBuf<T> coal_umin; DevBuf<uint32_t> coal_tile_flag; DevBuf<unsigned long long> coal_pv_disagree;
   hipEvent_t ev_umin_fork = nullptr, ev_umin = nullptr;
   bool umin_pending = false, umin_made = false;          // (launched and not yet joined by `st`; launched in this step_async)
-  uint64_t pv_call_of = 0, pv_seed_of = 0, pv_cells_of = 0; size_t pv_npart_of = 0;
-  int pv_used = 0, pv_fallback = 0; size_t pv_tiles = 0; // ("raw_coal_prevote", of the last step_async)
+  struct { coal_prevote_key of; int used = 0, fallback = 0; size_t tiles = 0; } pv;      // (used, fallback, tiles: "raw_coal_prevote", of the last step_async)
   void join_umin() { if (umin_pending) { umin_pending = false; HIPCHK(hipStreamWaitEvent(st, ev_umin, 0)); } }
   // ---- one wave per kept cell instead of the tiles (round 11; k_coal_cells, EXPERIMENTS.md 7.17) ----
   // The vote also lists the kept cells and counts {cells with a pair, kept cells, pairs, pairs in kept cells, tiles flagged on}; the counts come back
-  // as the sample does (a pinned copy behind the launch, polled by the next step_async, never waited for).  The launch that is handed the flags is
-  // k_coal_cells where the last polled vote kept at most COAL_CELLS_MAX_PERCENT of the cells that hold a pair, else k_coal_ranked<.., TILES>; the
-  // first launch of an object and the first after a restore know no vote and take the tiles.  The same bits either way.
-  // COAL_CELLS_MAX_PERCENT, the break-even of the two launches (EXPERIMENTS.md 7.17; kernel trace, 64^3 x 64, f64, 32 768 tiles, us per launch):
-  //   box (steps 2-8)            cells kept   tiles flagged on   k_coal_cells   k_coal_ranked<.., TILES>
-  //   stratocumulus              0.1 %        1 %                13             38
-  //   sparse (--dt 0.05)         16-19 %      91-95 %            148-168        280-284
-  //   mixed (--dt 0.02)          50 %         52 %               412-425        197-202
-  //   coal-stress --dt 0.045     100 %        100 %              804-824        348-358
-  // The list form costs 10 us + 3.1 ns per kept cell; the tiles cost 1.07 ns per tile (the walk over the flags: 35 us here, 0.22 ms at 128^3) +
-  // 9.6 ns per tile flagged on.  How many tiles a kept cell flags depends on how the kept cells lie: scattered (sparse) each flags a tile of its
-  // own and the list form wins at 19 % and beyond; side by side (mixed: eight kept cells per kept tile) the lines cross at
-  // 10 + 800 x = 38 + 330 x, x = 6 % of the cells.  The threshold is the lower of the two, so that no layout pays.
-  static constexpr unsigned long long COAL_CELLS_MAX_PERCENT = 6;
-  DevBuf<uint32_t> coal_kept_cells; DevBuf<unsigned long long> coal_vote_cnt; void *cells_pinned = nullptr; hipEvent_t ev_cells = nullptr;
-  bool cells_vote_pending = false, cells_vote_of_list = false, cells_vote_known = false, cells_listed = false;
-  unsigned long long cells_kept = 0, cells_with_pair = 0, cells_tiles_sent = 0;
+  // as the sample does, never waited for, and choose between k_coal_cells and k_coal_ranked<.., TILES> (coal_adapt::list_wanted).
+  DevBuf<uint32_t> coal_kept_cells; DevBuf<unsigned long long> coal_vote_cnt; HostSample cells_vote;
+  bool cells_vote_of_list = false, cells_listed = false;
+  unsigned long long cells_tiles_sent = 0;
   int last_coal_cells = 0;                   // ("raw_coal_cells": the coalescence launches of the last step_async in the list form)
   void poll_cells_vote()
   {
-    if (!cells_vote_pending || hipEventQuery(ev_cells) != hipSuccess) return;
-    cells_vote_pending = false;
-    const unsigned long long *h = static_cast<const unsigned long long *>(cells_pinned);
+    const unsigned long long *h = cells_vote.arrived();
+    if (!h) return;
     const coal_vote_sums v = coal_vote_sums_of(h);
-    cells_vote_known = true; cells_with_pair = v.with_pair; cells_kept = v.kept;
+    adapt.vote(v.kept, v.with_pair);
     if (!cells_vote_of_list) return;         // (a launch of the tiles has fed the sample itself)
     if (dbg2(LCX_DBG2_COAL_CELL_LIST_ALWAYS)) return;       // (tests: a forced launch stays forced -- counted per cell, a box that keeps every cell skips no pair)
     // the list form feeds the two pause rules from the vote's exact counts: pairs of cells voted off count as skipped, all pairs as examined,
     // tiles flagged off as left, tiles as launched
-    const unsigned long long examined = v.pairs, skipped = v.pairs - v.pairs_kept, launched = cells_tiles_sent, left = launched - v.tiles_on;
-    if (examined && skipped * COAL_SKIP_MIN_SHARE < examined) skip_pause = COAL_SKIP_PAUSE;
-    if (launched && left * 100 < launched * COAL_EXIT_MIN_PERCENT) exit_pause = COAL_EXIT_PAUSE;
-  }
-  bool cells_list_wanted() const
-  {
-    return dbg2(LCX_DBG2_COAL_CELL_LIST_ALWAYS) || (cells_vote_known && cells_kept * 100 <= cells_with_pair * COAL_CELLS_MAX_PERCENT);
+    adapt.feed(v.pairs - v.pairs_kept, v.pairs, cells_tiles_sent - v.tiles_on, cells_tiles_sent);
   }
   bool coal_bound_armed = false;             // step_async's own hskpng_vterm has just left the maxima: the FIRST coalescence substep may use them
   int last_coal_skip = 0;                    // ("raw_coal_skip": the coalescence launches of the last step_async that used a bound)
@@ -649,10 +644,7 @@ struct Particles : IParticles {
     if (st) (void)hipStreamDestroy(st);
     if (pinned) (void)hipHostFree(pinned);
     if (diag_stage) (void)hipHostFree(diag_stage);
-    if (skip_pinned) (void)hipHostFree(skip_pinned);
-    if (ev_skip) (void)hipEventDestroy(ev_skip);
-    if (cells_pinned) (void)hipHostFree(cells_pinned);
-    if (ev_cells) (void)hipEventDestroy(ev_cells);
+    skip_sample.release(); cells_vote.release();
     // (the copy stream reads the staging areas: it is drained before they are freed)
     if (st_copy) { (void)hipStreamSynchronize(st_copy); (void)hipStreamDestroy(st_copy); }
     for (HostStage *h : {&hstage_in, &hstage_out}) if (h->p) (void)hipHostFree(h->p);
@@ -1237,12 +1229,10 @@ struct Particles : IParticles {
         refresh_cmax_floor();                          // (the maxima start from the floor pair, and the pass offers only above it)
         hipLaunchKernelGGL(k_fill_pairs, dim3(nblk(ncell)), dim3(BS), 0, st, coal_cmax.p, size_t(ncell), (const uint32_t *)coal_floor.p);
         auto launch_max = [&](auto kern) { hipLaunchKernelGGL(kern, gv, dim3(BS), 0, st, nphys, 0, vtc, A.rw2.p, ijk.p, vt_pre.p, vt_0.p, A.vt.p, coal_cmax.p, (const uint32_t *)coal_floor.p); };
-        if (o.strict_fp) { if (table) launch_max(k_vterm_b77<T, false, true, true>); else launch_max(k_vterm_b77<T, false, false, true>); }
-        else             { if (table) launch_max(k_vterm_b77<T, true, true, true>); else launch_max(k_vterm_b77<T, true, false, true>); }
+        with_bool(!o.strict_fp, table, [&](auto fast, auto tab) { launch_max(k_vterm_b77<T, decltype(fast)::value, decltype(tab)::value, true>); });
         return true;
       }
-      if (o.strict_fp) { if (table) launch(k_vterm_b77<T, false, true>); else launch(k_vterm_b77<T, false, false>); }
-      else             { if (table) launch(k_vterm_b77<T, true, true>); else launch(k_vterm_b77<T, true, false>); }
+      with_bool(!o.strict_fp, table, [&](auto fast, auto tab) { launch(k_vterm_b77<T, decltype(fast)::value, decltype(tab)::value>); });
       return false;
     }
     hipLaunchKernelGGL(k_vterm<T>, dim3(nblk(nphys)), dim3(BS), 0, st, nphys, int(only_invalid), vtc, A.rw2.p, ijk.p, Tk.p, p.p, rhod.p, eta.p, vt_0.p, A.vt.p);
@@ -1485,10 +1475,9 @@ struct Particles : IParticles {
     const int ask = dbg(LCX_DBG_COND_NO_LIST) ? 0 : 1;
     const T kv = kpa_uniform ? kpa_value : T(0);
     last_cond_kernel = LCX_CK_SUBSTEPS;
-    if (toms && kpa_uniform) hipLaunchKernelGGL((k_cond_substeps<T, true, 2>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
-    else if (toms) hipLaunchKernelGGL((k_cond_substeps<T, false, 2>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
-    else if (kpa_uniform) hipLaunchKernelGGL((k_cond_substeps<T, true, 0>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
-    else hipLaunchKernelGGL((k_cond_substeps<T, false, 0>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
+    with_bool(kpa_uniform, toms, [&](auto uni, auto tm) {
+      hipLaunchKernelGGL((k_cond_substeps<T, decltype(uni)::value, decltype(tm)::value ? 2 : 0>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
+    });
     vtpre_valid = false;
   }
   // sstp_percell_step.ipp:7-48, as an argument of the substep's cell pass (k_cell_cond_pre)
@@ -1628,13 +1617,14 @@ struct Particles : IParticles {
             // (the host does not know the counts: workgroups for 1 % of the droplets -- the settled boxes list 0.1 %, a swinging one 1 % -- at a droplet per lane,
             // more droplets by the stride; a workgroup that finds nothing leaves at once)
             const unsigned per_part = unsigned(std::min<size_t>(2048, std::max<size_t>(8, lst.shard_cap / 100 / BS + 1)));
-            if (lst.rec) {
-              const unsigned n_resume = DEFER_SHARDS * ((lst.rec_cap + BS - 1) / BS);
-              if (uni) hipLaunchKernelGGL((k_cond_lean_resume<T, true>), dim3(n_resume), bl, 0, st, a, lst, kv);
-              else hipLaunchKernelGGL((k_cond_lean_resume<T, false>), dim3(n_resume), bl, 0, st, a, lst, kv);
-            }
-            if (uni) hipLaunchKernelGGL((k_cond_lean_listed<T, true>), dim3(DEFER_SHARDS * per_part), bl, 0, st, a, lst, kv);
-            else hipLaunchKernelGGL((k_cond_lean_listed<T, false>), dim3(DEFER_SHARDS * per_part), bl, 0, st, a, lst, kv);
+            with_bool(uni, [&](auto u) {
+              constexpr bool UNI = decltype(u)::value;
+              if (lst.rec) {
+                const unsigned n_resume = DEFER_SHARDS * ((lst.rec_cap + BS - 1) / BS);
+                hipLaunchKernelGGL((k_cond_lean_resume<T, UNI>), dim3(n_resume), bl, 0, st, a, lst, kv);
+              }
+              hipLaunchKernelGGL((k_cond_lean_listed<T, UNI>), dim3(DEFER_SHARDS * per_part), bl, 0, st, a, lst, kv);
+            });
           };
         }
       }
@@ -1745,13 +1735,10 @@ struct Particles : IParticles {
     if (!o.sstp_cond_mix) {
       {
         Range r(this, o.adaptive_sstp_cond ? "cond_perparticle_adaptive" : "cond_perparticle");
-        if (o.adaptive_sstp_cond) {
-          if (o.strict_fp) hipLaunchKernelGGL((k_pp_cond_adaptive<T, false>), grid, blk, 0, st, npart, a);
-          else             hipLaunchKernelGGL((k_pp_cond_adaptive<T, true>), grid, blk, 0, st, npart, a);
-        } else {
-          if (o.strict_fp) hipLaunchKernelGGL((k_pp_cond_nomix<T, false>), grid, blk, 0, st, npart, a);
-          else             hipLaunchKernelGGL((k_pp_cond_nomix<T, true>), grid, blk, 0, st, npart, a);
-        }
+        with_bool(!o.strict_fp, [&](auto fast) {
+          if (o.adaptive_sstp_cond) hipLaunchKernelGGL((k_pp_cond_adaptive<T, decltype(fast)::value>), grid, blk, 0, st, npart, a);
+          else hipLaunchKernelGGL((k_pp_cond_nomix<T, decltype(fast)::value>), grid, blk, 0, st, npart, a);
+        });
       }
       // save_liq_ice_content_before_change + calc_liq_ice_content_change + update_th_rv: ordered per-cell sums of n rw^3
       Range r(this, "cond_cellfinish");
@@ -1765,8 +1752,7 @@ struct Particles : IParticles {
     a.drv = m3_before.p; a.dth = m3_after.p; a.dst_rv = pp_dst_rv.p; a.dst_th = pp_dst_th.p;
     for (int step = 0; step < sstp_cond; ++step) {
       a.step = step;
-      if (o.strict_fp) hipLaunchKernelGGL((k_pp_cond_mix<T, false>), grid, blk, 0, st, npart, a);
-      else             hipLaunchKernelGGL((k_pp_cond_mix<T, true>), grid, blk, 0, st, npart, a);
+      with_bool(!o.strict_fp, [&](auto fast) { hipLaunchKernelGGL((k_pp_cond_mix<T, decltype(fast)::value>), grid, blk, 0, st, npart, a); });
       hipLaunchKernelGGL(k_cell_seqsum<T>, dim3(nblk(ncell, cf_cells())), dim3(BS), 0, st, ncell, cf_cells(), cell_start.p, m3_before.p, dv.p, rhod.p, 0, pp_dst_rv.p);
       hipLaunchKernelGGL(k_cell_seqsum<T>, dim3(nblk(ncell, cf_cells())), dim3(BS), 0, st, ncell, cf_cells(), cell_start.p, m3_after.p, dv.p, rhod.p, 0, pp_dst_th.p);
     }
@@ -2395,19 +2381,18 @@ struct Particles : IParticles {
   // step_async, ahead of the velocity pass: the smallest draw of every cell's pairs, on the side stream (beside that pass: it waits for memory, this
   // kernel only multiplies integers).  Launched where the step's first coalescence launch will be the EXIT form as far as can be known here; the call
   // number is the one coal() will hand to rand_u01 -- the next one, or the one after where coal() draws the shuffle's salts first.  rng_call is not
-  // advanced.  What the draws were made for is kept with them, and coal() compares (a mismatch: round 9's launch, pv_fallback).
+  // advanced.  What the draws were made for is kept with them, and coal() compares (a mismatch: round 9's launch, pv.fallback).
   void launch_umin(bool want_bound)
   {
-    umin_made = false; pv_used = 0; pv_fallback = 0; pv_tiles = 0;
-    const bool exit_form = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
-    if (!want_bound || !exit_form || dbg2(LCX_DBG2_NO_COAL_PREVOTE) || npart < 2 || !ncell) return;
+    umin_made = false; pv.used = 0; pv.fallback = 0; pv.tiles = 0;
+    if (!want_bound || !adapt.prevote_wanted(coal_tg()) || npart < 2 || !ncell) return;
     make_side_stream();
     if (!ev_umin) { HIPCHK(hipEventCreateWithFlags(&ev_umin_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_umin, hipEventDisableTiming)); }
     coal_umin.alloc(ncell);
-    pv_call_of = rng_call + 1 + (coal_owes_unshuffled_cells() ? 1 : 0); pv_seed_of = uint64_t(uint32_t(seed_now())); pv_cells_of = cells_version; pv_npart_of = npart;
+    pv.of = coal_prevote_key{rng_call + 1 + (coal_owes_unshuffled_cells() ? 1 : 0), uint64_t(uint32_t(seed_now())), cells_version, npart};
     HIPCHK(hipEventRecord(ev_umin_fork, st));                  // (cell_start is final since the last scan, on `st`)
     HIPCHK(hipStreamWaitEvent(st_rank, ev_umin_fork, 0));
-    hipLaunchKernelGGL(k_coal_umin<T>, dim3(nblk(ncell * 8)), dim3(BS), 0, st_rank, ncell, (const uint32_t *)cell_start.p, pv_call_of, pv_seed_of, coal_umin.p);
+    hipLaunchKernelGGL(k_coal_umin<T>, dim3(nblk(ncell * 8)), dim3(BS), 0, st_rank, ncell, (const uint32_t *)cell_start.p, pv.of.call, pv.of.seed, coal_umin.p);
     HIPCHK(hipEventRecord(ev_umin, st_rank));
     umin_pending = umin_made = true;
   }
@@ -2430,120 +2415,109 @@ struct Particles : IParticles {
     Range r(this, "coal");
     const u01_src<T> rs = rand_u01(npart);
     if (ix_tag >= 0) record_rng(rs);
+    // which launch (lcx_coal_plan.hpp): everything below reads the form and decides nothing again
+    const coal_toggles tg = coal_tg();
+    coal_plan_in in = coal_plan_in_of(adapt, tg);
+    in.first_substep = first_substep; in.order_owed = coal_ranks_owed_order(); in.replayed = rs.arr != nullptr;
+    in.bound_armed = bound_armed; in.n_max_stale = n_max_stale;
+    in.prevote_usable = umin_made && pv.of == coal_prevote_key{rs.call, rs.seed, cells_version, npart};
+    const coal_form form = coal_form_of(in);
+    // diss == nullptr stands for the reference's constant-zero dissipation rate when opts.turb_coal is off (coal.ipp:392-403,439-451)
+    coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
     // The order this coalescence pairs up is still owed (hskpng_sort_helper has found it `fresh` and ranked nothing): the kernel that ranks
     // for itself takes the cells as the scatter left them.  The debt stays -- sorted_id in memory is in arrival order -- until somebody
     // reads the order (pay_rank) or the step's re-sort makes it void.
-    if (first_substep && coal_ranks_owed_order() && !rs.arr) {
-      coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
+    if (form != coal_form::PAIRS) {
+      const bool bound = form != coal_form::RANKED, exits = bound && form != coal_form::RANKED_SKIP;
+      const bool flagged = form == coal_form::RANKED_TILES || form == coal_form::CELLS, by_cells = form == coal_form::CELLS;
       dim3 gr(unsigned((npart + COAL_RANKED_POS - 1) / COAL_RANKED_POS));              // (a workgroup per tile; with the tiles' flags: per COAL_TILES_PER_WG tiles)
       last_coal_kernel = coal_marks_dead ? 2 : 0; ++last_coal_ranked;
       coal_skip_args<T> ska{};
-      bool exits = false, by_cells = false;           // (by_cells: k_coal_cells over the vote's list in place of the tiles' launch)
       cells_listed = false;
-      if (bound_armed && !n_max_stale) {
-        const bool counted = dbg2(LCX_DBG2_COAL_SKIP_COUNT);
-        if (!counted) coal_skip_sample.alloc(128);
-        exits = !dbg2(LCX_DBG2_NO_COAL_RANK_EXIT) && (exit_pause == 0 || dbg2(LCX_DBG2_COAL_RANK_EXIT_ALWAYS));
-        if (!exits && exit_pause > 0) --exit_pause;
+      if (bound) {
+        if (!tg.counted) coal_skip_sample.alloc(128);
+        adapt.exit_launch_done(exits);
         if (exits) ++last_coal_exit;
-        // the cells' vote (round 10): the draws that step_async had made beside the velocity pass, if they are this launch's; the flags of the tiles
-        const uint32_t *flags = nullptr;
         if (exits && umin_made) {
           umin_made = false;
           join_umin();
-          if (pv_call_of == rs.call && pv_seed_of == rs.seed && pv_cells_of == cells_version && pv_npart_of == npart) {
-            coal_tile_flag.alloc(gr.x);
-            HIPCHK(hipMemsetAsync(coal_tile_flag.p, 0, size_t(gr.x) * sizeof(uint32_t), st));
-            coal_vote_out vo{nullptr, nullptr, 0};
-            if (!dbg2(LCX_DBG2_NO_COAL_CELL_LIST)) {                 // (the vote also lists the kept cells and counts what the host chooses the form by)
-              coal_kept_cells.alloc(CV_SLOTS * coal_sublist_cap(ncell, WAVE)); coal_vote_cnt.alloc(CV_WORDS);
-              HIPCHK(hipMemsetAsync(coal_vote_cnt.p, 0, CV_WORDS * sizeof(unsigned long long), st));
-              vo = coal_vote_out{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE)};
-            }
-            cells_listed = vo.list != nullptr;
-            hipLaunchKernelGGL(k_coal_cellvote<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const uint32_t *)cell_start.p, (const uint32_t *)coal_cmax.p, (const T *)dv.p,
-                               (const T *)coal_umin.p, (const n_t *)coal_n_max.p, (const T *)coal_emax.p, n_emax, T(kernel_r_max), T(dt_sub), coal_tile_flag.p, uint64_t(gr.x), vo);
-            flags = coal_tile_flag.p; pv_tiles = gr.x; ++pv_used;
-            by_cells = cells_listed && !counted && cells_list_wanted();
-          }
-          else ++pv_fallback;     // (defensive: no path reaches it today -- step_async asks for a bound only where coal() neither re-sorts nor draws
-                                  // anything but the salts counted above, and no test takes it; it keeps a later change to either from using stale draws)
+          if (!flagged) ++pv.fallback;   // (defensive: no path reaches it today -- step_async asks for a bound only where coal() neither re-sorts nor draws
+                                         // anything but the salts counted in the key, and no test takes it; it keeps a later change to either from using stale draws)
         }
-        if (!counted && !by_cells) HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 128 * sizeof(unsigned long long), st));       // (the list form feeds no sample)
-        ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, counted ? coal_skip_cnt.p : nullptr, counted ? nullptr : coal_skip_sample.p,
-                                counted && exits ? coal_skip_cnt.p + 2 : nullptr, flags, counted && flags ? coal_pv_disagree.p : nullptr};
-        if (flags) gr.x = (gr.x + COAL_TILES_PER_WG - 1) / COAL_TILES_PER_WG;
-        if (counted && !exits) coal_wg_no_exit += gr.x;
+        // the cells' vote (round 10): the draws that step_async had made beside the velocity pass are this launch's; the flags of the tiles
+        if (flagged) {
+          coal_tile_flag.alloc(gr.x);
+          HIPCHK(hipMemsetAsync(coal_tile_flag.p, 0, size_t(gr.x) * sizeof(uint32_t), st));
+          coal_vote_out vo{nullptr, nullptr, 0};
+          if (in.listed) {                                         // (the vote also lists the kept cells and counts what the host chooses the form by)
+            coal_kept_cells.alloc(CV_SLOTS * coal_sublist_cap(ncell, WAVE)); coal_vote_cnt.alloc(CV_WORDS);
+            HIPCHK(hipMemsetAsync(coal_vote_cnt.p, 0, CV_WORDS * sizeof(unsigned long long), st));
+            vo = coal_vote_out{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE)};
+          }
+          cells_listed = in.listed;
+          hipLaunchKernelGGL(k_coal_cellvote<T>, dim3(nblk(ncell)), dim3(BS), 0, st, ncell, (const uint32_t *)cell_start.p, (const uint32_t *)coal_cmax.p, (const T *)dv.p,
+                             (const T *)coal_umin.p, (const n_t *)coal_n_max.p, (const T *)coal_emax.p, n_emax, T(kernel_r_max), T(dt_sub), coal_tile_flag.p, uint64_t(gr.x), vo);
+          pv.tiles = gr.x; ++pv.used;
+        }
+        if (!tg.counted && !by_cells) HIPCHK(hipMemsetAsync(coal_skip_sample.p, 0, 128 * sizeof(unsigned long long), st));       // (the list form feeds no sample)
+        ska = coal_skip_args<T>{coal_cmax.p, coal_n_max.p, coal_emax.p, n_emax, tg.counted ? coal_skip_cnt.p : nullptr, tg.counted ? nullptr : coal_skip_sample.p,
+                                tg.counted && exits ? coal_skip_cnt.p + 2 : nullptr, flagged ? coal_tile_flag.p : nullptr, tg.counted && flagged ? coal_pv_disagree.p : nullptr};
+        if (flagged) gr.x = (gr.x + COAL_TILES_PER_WG - 1) / COAL_TILES_PER_WG;
+        if (tg.counted && !exits) coal_wg_no_exit += gr.x;
         ++last_coal_skip;
       }
       // (with a bound: the form whose workgroups leave ahead of the ranking where they keep no pair; LCX_DBG2_NO_COAL_RANK_EXIT, or the last
       // counters showed too few leaving: round 8's form.  With the collision rates on: the same form, tallying)
-      auto launch_all = [&](auto tallies) {
-        constexpr bool TL = decltype(tallies)::value;
+      with_bool(coal_marks_dead, cr.on, [&](auto mark, auto tallies) {
+        constexpr bool MK = decltype(mark)::value, TL = decltype(tallies)::value;
         coal_tally_arg<T, TL> ta{};
         if constexpr (TL) ta = cr_arg();
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
                              deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
         };
-        if (by_cells) {
-          const coal_cells_args ca{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE), coal_cmax.p, coal_n_max.p, n_emax,
-                                   dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? uint32_t(WAVE) : uint32_t(CELLRANK_MAX)};
-          const dim3 gc(unsigned(coal_cells_grid(ncell, COAL_CELLS_WAVES, dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? 1 : COAL_CELLS_GRID_CAP)));
-          auto launch_cells = [&](auto kern) {
-            hipLaunchKernelGGL(kern, gc, dim3(BS), 0, st, ca, (const T *)coal_emax.p, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)cell_start.p, deferred_rs,
-                               A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ta);
-          };
-          if (coal_marks_dead) launch_cells(k_coal_cells<T, true, TL>); else launch_cells(k_coal_cells<T, false, TL>);
+        switch (form) {
+          case coal_form::CELLS: {
+            const coal_cells_args ca{coal_kept_cells.p, coal_vote_cnt.p, coal_sublist_cap(ncell, WAVE), coal_cmax.p, coal_n_max.p, n_emax,
+                                     dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? uint32_t(WAVE) : uint32_t(CELLRANK_MAX)};
+            const dim3 gc(unsigned(coal_cells_grid(ncell, COAL_CELLS_WAVES, dbg2(LCX_DBG2_COAL_CELL_LIST_SMALL) ? 1 : COAL_CELLS_GRID_CAP)));
+            hipLaunchKernelGGL((k_coal_cells<T, MK, TL>), gc, dim3(BS), 0, st, ca, (const T *)coal_emax.p, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)cell_start.p,
+                               deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ta);
+            ++last_coal_cells;
+            break;
+          }
+          case coal_form::RANKED_TILES: launch(k_coal_ranked<T, MK, true, true, TL, true>); break;
+          case coal_form::RANKED_EXIT: launch(k_coal_ranked<T, MK, true, true, TL>); break;
+          case coal_form::RANKED_SKIP: launch(k_coal_ranked<T, MK, true, false, TL>); break;
+          default: launch(k_coal_ranked<T, MK, false, false, TL>);
         }
-        else if (ska.cmax && exits && ska.flags) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL, true>); else launch(k_coal_ranked<T, false, true, true, TL, true>); }
-        else if (ska.cmax && exits) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, true, TL>); else launch(k_coal_ranked<T, false, true, true, TL>); }
-        else if (ska.cmax) { if (coal_marks_dead) launch(k_coal_ranked<T, true, true, false, TL>); else launch(k_coal_ranked<T, false, true, false, TL>); }
-        else if (coal_marks_dead) launch(k_coal_ranked<T, true, false, false, TL>); else launch(k_coal_ranked<T, false, false, false, TL>);
-      };
-      if (cr.on) launch_all(std::true_type{}); else launch_all(std::false_type{});
-      if (by_cells) ++last_coal_cells;
-      if (cells_listed && !cells_vote_pending) {       // (the vote's counts on their way to the host: poll_cells_vote)
-        if (!cells_pinned) { HIPCHK(hipHostMalloc(&cells_pinned, CV_WORDS * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_cells, hipEventDisableTiming)); }
-        HIPCHK(hipMemcpyAsync(cells_pinned, coal_vote_cnt.p, CV_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(ev_cells, st));
-        cells_vote_pending = true; cells_vote_of_list = by_cells; cells_tiles_sent = pv_tiles;
+      });
+      if (cells_listed && !cells_vote.pending) {       // (the vote's counts on their way to the host: poll_cells_vote)
+        cells_vote.send(coal_vote_cnt.p, CV_WORDS, CV_WORDS, st);
+        cells_vote_of_list = by_cells; cells_tiles_sent = pv.tiles;
       }
-      if (ska.cmax && !by_cells && !skip_sample_pending) {          // (the launch's counters on their way to the host: poll_skip_sample)
-        if (!skip_pinned) { HIPCHK(hipHostMalloc(&skip_pinned, 128 * sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev_skip, hipEventDisableTiming)); }
-        skip_sample_n = ska.cnt ? 4 : 128;
-        HIPCHK(hipMemcpyAsync(skip_pinned, ska.cnt ? ska.cnt : ska.sample, skip_sample_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(ev_skip, st));
-        skip_sample_pending = true;
-      }
+      if (bound && !by_cells && !skip_sample.pending)  // (the launch's counters on their way to the host: poll_skip_sample)
+        skip_sample.send(tg.counted ? coal_skip_cnt.p : coal_skip_sample.p, tg.counted ? 4 : 128, 128, st);
       return;
     }
     const bool onishi = o.kernel == LCX_KERNEL_ONISHI_HALL || o.kernel == LCX_KERNEL_ONISHI_HALL_DAVIS_NO_WAALS;
-    // diss == nullptr stands for the reference's constant-zero dissipation rate when opts.turb_coal is off (coal.ipp:392-403,439-451)
-    coal_kernel_cfg<T> kc{o.kernel, n_user_params, T(kernel_r_max), kparams.p, eta.p, rhod.p, turb_coal ? diss_rate.p : nullptr};
     const bool kappa_pass = o.n_dry_distros + n_size_keys > 1, chem_pass = o.chem_switch != 0;
-    auto launch = [&](auto kern, bool need_col = true) {
-      hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
-                         A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
-                         ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr, coal_tally_arg<T, false>{});
-    };
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
     const bool production = tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead;
-    if (cr.on) {                                        // the same three kernels, feeding the collision rates' accumulators
-      const coal_tally_arg<T, true> ta = cr_arg();
-      auto tally = [&](auto kern, bool need_col = true) {
+    with_bool(cr.on, [&](auto tallies) {                  // (with the collision rates on: the same three kernels, feeding their accumulators)
+      constexpr bool TL = decltype(tallies)::value;
+      coal_tally_arg<T, TL> ta{};
+      if constexpr (TL) ta = cr_arg();
+      auto launch = [&](auto kern, bool need_col = true) {
         hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
                            A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
                            ix_ict >= 0 ? A.ext[ix_ict].p : nullptr, coal_marks_dead ? ijk.p : nullptr, ta);
       };
-      if (onishi) { last_coal_kernel = 1; tally(k_coal<T, true, false, true>); }
-      else if (production) { last_coal_kernel = 2; tally(k_coal<T, false, true, true>, kappa_pass || chem_pass); }
-      else { last_coal_kernel = 0; tally(k_coal<T, false, false, true>); }
-    }
-    else if (onishi) { last_coal_kernel = 1; launch(k_coal<T, true>); }
-    // (the production kernel writes the collision record only for the kappa pass: nothing else reads it outside a replayed run)
-    else if (production) { last_coal_kernel = 2; launch(k_coal<T, false, true>, kappa_pass || chem_pass); }
-    else { last_coal_kernel = 0; launch(k_coal<T, false>); }
+      if (onishi) { last_coal_kernel = 1; launch(k_coal<T, true, false, TL>); }
+      // (the production kernel writes the collision record only for the kappa pass: nothing else reads it outside a replayed run)
+      else if (production) { last_coal_kernel = 2; launch(k_coal<T, false, true, TL>, kappa_pass || chem_pass); }
+      else { last_coal_kernel = 0; launch(k_coal<T, false, false, TL>); }
+    });
     if (kappa_pass)
       hipLaunchKernelGGL(k_coal_kappa<T>, dim3(nblk(npart)), dim3(BS), 0, st, npart, sid(), col.p, A.kpa.p, A.rd3.p);
     if (chem_pass)                                                                       // coal.ipp:458-480
@@ -2585,10 +2559,7 @@ struct Particles : IParticles {
     if (reindex) zero_n_unmarked = false;
     const bool pc = adve_scheme == LCX_ADVE_PRED_CORR, tb = a.up != nullptr;
     last_move_kernel = (pc ? 16 : 0) | (tb ? 32 : 0);              // ("raw_move_kernel": PC, TURB; SPEC is added where one is chosen)
-    if (pc && tb) hipLaunchKernelGGL((k_move<T, true, true>), dim3(blocks), dim3(BS), 0, st, a);
-    else if (pc) hipLaunchKernelGGL((k_move<T, true, false>), dim3(blocks), dim3(BS), 0, st, a);
-    else if (tb) hipLaunchKernelGGL((k_move<T, false, true>), dim3(blocks), dim3(BS), 0, st, a);
-    else if (n_dims == 3) {
+    if (!pc && !tb && n_dims == 3) {
       const bool full = do_adve && do_sedi && !do_subs && do_bcnd && reindex && halo == 0 && !o.open_side_walls && !o.periodic_topbot_walls &&
                         (adve_scheme == LCX_ADVE_EULER || adve_scheme == LCX_ADVE_IMPLICIT);
       const int spec = !full ? MOVE_3D : MOVE_3D | MOVE_FULL | (a.distmem ? MOVE_DISTMEM : 0) | (adve_scheme == LCX_ADVE_IMPLICIT ? MOVE_IMPLICIT : 0);
@@ -2601,7 +2572,7 @@ struct Particles : IParticles {
         default: hipLaunchKernelGGL((k_move<T, false, false, MOVE_3D>), dim3(blocks), dim3(BS), 0, st, a);
       }
     }
-    else hipLaunchKernelGGL((k_move<T, false, false>), dim3(blocks), dim3(BS), 0, st, a);
+    else with_bool(pc, tb, [&](auto p_c, auto turb) { hipLaunchKernelGGL((k_move<T, decltype(p_c)::value, decltype(turb)::value>), dim3(blocks), dim3(BS), 0, st, a); });
     if (reindex && !distmem() && !hold_big_list) list_big_from_hist();  // (with neighbours: after their immigrants are in, exch_unpack;
                                                                         // hold_big_list: after the aerosol source's newcomers are in, step_async)
     if (want_puddle && dev_exchange) puddle_pending_blocks = blocks;      // (reduced after the emigrants are on their way, see lcx_multi.hpp)
@@ -3418,8 +3389,7 @@ struct Particles : IParticles {
     // (the velocity pass leaves the per-cell maxima of coal_pair's bound where the first coalescence substep, right behind it, will rank for itself:
     // nothing in between writes rw2, vt, n or the cells)
     poll_skip_sample(); poll_cells_vote();
-    const bool paused = opts.coal && skip_pause > 0;
-    if (paused) --skip_pause;
+    const bool paused = adapt.bound_step(opts.coal);
     const bool want_bound = opts.coal && !paused && coal_skip_wanted();
     if (want_bound) refresh_n_max();
     launch_umin(want_bound);
@@ -3696,8 +3666,8 @@ struct Particles : IParticles {
     else if (s == "raw_coal_exit") v.assign(1, (unsigned long long)last_coal_exit);
     else if (s == "raw_coal_prevote") {            // of the last step_async: launches handed the tiles' flags, tiles flagged off, tiles, launches that fell back; LCX_DBG2_COAL_SKIP_COUNT: + disagreements
       unsigned long long off = 0;
-      if (pv_used && pv_tiles) { auto h = d2h(coal_tile_flag.p, pv_tiles); for (auto x : h) off += x == 0u; }
-      v = {(unsigned long long)pv_used, off, (unsigned long long)pv_tiles, (unsigned long long)pv_fallback};
+      if (pv.used && pv.tiles) { auto h = d2h(coal_tile_flag.p, pv.tiles); for (auto x : h) off += x == 0u; }
+      v = {(unsigned long long)pv.used, off, (unsigned long long)pv.tiles, (unsigned long long)pv.fallback};
       if (dbg2(LCX_DBG2_COAL_SKIP_COUNT)) v.push_back(coal_pv_disagree.p ? d2h(coal_pv_disagree.p, 1)[0] : 0ull);
     }
     else if (s == "raw_coal_cells") {              // of the last step_async: launches in the list form (k_coal_cells), kept cells, cells with a pair (its vote's; 0 without a list)
@@ -4542,8 +4512,8 @@ struct Particles : IParticles {
       }
       deferred_rs.un = nullptr; last_shuffle_rs.un = nullptr;
       should_now_run_async = should_now_run_cond = selected_before_counting = false;
-      skip_pause = 0; exit_pause = 0; skip_sample_pending = false; rank_pending = false; umin_made = false; pv_used = 0; pv_fallback = 0; pv_tiles = 0;
-      cells_vote_pending = cells_vote_known = cells_listed = false; cells_kept = cells_with_pair = 0; last_coal_cells = 0;
+      adapt = coal_adapt{}; skip_sample.pending = cells_vote.pending = false; rank_pending = false; umin_made = false; pv.used = 0; pv.fallback = 0; pv.tiles = 0;
+      cells_listed = false; last_coal_cells = 0;
       sync();
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)
