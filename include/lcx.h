@@ -272,6 +272,14 @@ enum lcx_cond_kernel {
   LCX_CK_PER_PARTICLE = 12,            /* exact_sstp_cond: k_pp_cond_* */
   LCX_CK_SUBSTEPS = 13                 /* k_cond_substeps: fast arithmetic, sstp_cond > 1 -- every substep of the step in one launch */
 };
+/* lcx_get_state_u64("raw_cond_finish") = { the form of the object's last per-cell finish of a condensation launch } (not part of a snapshot) */
+enum lcx_cond_finish {
+  LCX_CF_NONE = 0,                     /* none yet, or k_cond_substeps, which finishes its cells itself */
+  LCX_CF_ORDERED = 1,                  /* k_cond_cellfinish<T, 1>: strict arithmetic, the reference's summation order */
+  LCX_CF_LANES8 = 2,                   /* k_cond_cellfinish<T, 8>: eight lanes per cell through the LDS stage (a gather, or LCX_DBG_FINISH_STAGED) */
+  LCX_CF_DIRECT = 3,                   /* k_cond_cellfinish_direct: the droplets' changes lie in the sorted order */
+  LCX_CF_WAVE = 4                      /* k_cond_cellfinish_wave: a wave per cell, from 4096 cells at 192 droplets per cell */
+};
 
 /* one entry of src_dry_distros_t (opts.hpp): spectrum of the source PER SECOND, number of super-droplets (= size bins) it adds per
  * cell of the source box, and the number of steps between two firings */

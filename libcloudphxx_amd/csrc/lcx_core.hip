@@ -39,6 +39,7 @@
 #include "lcx_pool.hpp"
 #include "lcx_coal_floor_probe.h"
 #include "lcx_coal_plan.hpp"
+#include "lcx_cond_plan.hpp"
 
 // every kernel launch of this translation unit and every host wait for a stream are COUNTED (lcx_get_state_u64 "raw_launches"): what a
 // step costs a thin slab or a 2-D set-up is its launches and its waits, not its bytes (bench.py's c2 leg reports both per step)
@@ -366,7 +367,10 @@ struct Particles : IParticles {
   bool replay_used = false;   // a parity run: storage stays in the reference's id order (see opts_init.reorder_every)
   bool dbg2(unsigned f) const { return (o.dbg_flags2 & f) != 0; }
   bool dbg(unsigned f) const { return (o.dbg_flags & f) != 0; }      // test / measurement switches (include/lcx.h, lcx_dbg): read from the options, never from the environment
-  bool no_cond_pre = dbg(LCX_DBG_NO_COND_PRE);   // test switch: evaluate the per-cell set-up per droplet instead
+  // ---- what the condensation settles on the host (lcx_cond_plan.hpp): the switches as bools, dbg_cond_budget decoded ----
+  const cond_toggles ctg{o.dbg_flags, o.strict_fp != 0, o.cond_solver, o.exact_sstp_cond != 0};
+  const cond_budget cbudget{o.dbg_cond_budget};
+  static_assert(cond_budget::FOLD_STAGE == FOLD_CAP, "the plan's default is the fold kernel's stage");
   uint64_t cells_version = 0;   // order_cells: the list of cells above CELLRANK_MAX is remembered per cell_start
   bool exact = false, use_rc2 = false; int sstp_cond_act = 1, n_ext = 0, ix_rv = -1, ix_th = -1, ix_rh = -1, ix_p = -1, ix_rc2 = -1;
   DevBuf<T> pp_dlt[4], pp_rw3s, pp_dst_rv, pp_dst_th;
@@ -1406,7 +1410,7 @@ struct Particles : IParticles {
     const bool preshuffle = !strict_order && !o.strict_fp && last_async_coal && o.coal_switch && !reorder_due && npart >= 2;
     // (the scatter rides on the next condensation kernel when that will be the storage-order one and no re-ordering is due -- round 4: a
     // slab with neighbours as well, once its immigrants are in the histogram; its exchange then skips the overlapped interior re-sort)
-    const bool defer = defer_sort_ok && lean_storage_cond() && !reorder_due && meta_p != nullptr && replay.empty();
+    const bool defer = defer_sort_ok && ctg.lean_storage() && !reorder_due && meta_p != nullptr && replay.empty();
     sort_from_hist(preshuffle, meta_p, defer);
     shuffle_fresh = preshuffle && !sort_deferred;
     // dropping the dead SDs costs one pass over all attributes either way: gather it in sorted order (opts_init.reorder_every)
@@ -1468,14 +1472,12 @@ struct Particles : IParticles {
     cond_args<T> a{sid(), sijk(), A.n.p, A.rd3.p, A.kpa.p, A.vt.p, A.rw2.p, rhod.p, rv.p, Tk.p, eta.p, RH.p,
                    lambda_D.p, lambda_K.p, m3_before.p, m3_after.p, T(T(dt) / sstp_cond), T(RH_max), eps_tol, T(2.), 100u, 1, ncell,
                    0u, nullptr, P.pre, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
-    const unsigned per_cell = unsigned(std::max<size_t>(1, npart / std::max<size_t>(1, ncell)));
-    const unsigned cells_per_wg = std::max(1u, std::min(unsigned(SUBSTEP_CELLS), unsigned(BS) / per_cell));
+    const unsigned cells_per_wg = cond_substeps_cells_per_wg(npart, ncell, BS, SUBSTEP_CELLS);
     const dim3 grid(nblk(ncell, cells_per_wg)), bl(BS);
-    const bool toms = o.cond_solver == 1;
-    const int ask = dbg(LCX_DBG_COND_NO_LIST) ? 0 : 1;
+    const int ask = ctg.no_list ? 0 : 1;
     const T kv = kpa_uniform ? kpa_value : T(0);
-    last_cond_kernel = LCX_CK_SUBSTEPS;
-    with_bool(kpa_uniform, toms, [&](auto uni, auto tm) {
+    last_cond_kernel = LCX_CK_SUBSTEPS; last_cond_finish = LCX_CF_NONE;      // (the kernel finishes its cells itself)
+    with_bool(kpa_uniform, ctg.toms(), [&](auto uni, auto tm) {
       hipLaunchKernelGGL((k_cond_substeps<T, decltype(uni)::value, decltype(tm)::value ? 2 : 0>), grid, bl, 0, st, P, a, kv, cell_start.p, cells_per_wg, sstp_cond, sstp_fused(0), rw_mom3.p, ask);
     });
     vtpre_valid = false;
@@ -1487,21 +1489,23 @@ struct Particles : IParticles {
     if (sstp_cond > 1) ss.n = var_rho ? 3 : 2;
     return ss;
   }
-  bool lean_storage_cond() const
-  { return !o.strict_fp && !no_cond_pre && cond_storage_order && !cond_toms_two_pass() && !o.exact_sstp_cond; }
-  bool cond_toms_two_pass() const { return o.cond_solver == 1 && dbg(LCX_DBG_COND_TOMS_TWO_PASS); }
+  // the second half of a lean launch: the listed droplets (brackets that may hold several roots) take the reference's iterates in
+  // k_cond_lean_listed, behind k_cond_lean_resume where the first pass left records.  What cond_substep keeps of the first half until the
+  // fork of the in-cell ranking is behind it: the list, the kernels' UNI and kappa, the two grids (lcx_cond_plan.hpp)
+  struct cond_listed_pass { bool on = false, uni = false; cond_list lst{}; T kv = T(0); unsigned per_part = 0, n_resume = 0; };
   void cond_substep(double RH_max, int step, bool turb_cond = false)
   {
-    const bool carry_scatter = sort_deferred && lean_storage_cond() && !turb_cond && npart;
+    const bool carry_scatter = ctg.carries_scatter(sort_deferred, turb_cond, npart);
     if (!carry_scatter) hskpng_sort();
+    // which kernel (lcx_cond_plan.hpp): everything below reads the plan and decides nothing again
+    const cond_kernel_plan kp = cond_kernel_of(ctg, cbudget, turb_cond, kpa_uniform);
     // fast arithmetic (no SGS supersaturation): per-cell set-up hoisted (k_cond_cellpre) and one scratch value per droplet (the
     // change of n rw^3); strict arithmetic: n rw^3 before and after in position order + the ordered per-cell walk
-    const bool fast = !o.strict_fp && !turb_cond && !no_cond_pre;
+    const bool fast = kp.fast;
     {
       // the substep's cell pass in one launch: mean free paths (substep 0, from the previous T and p as the reference's hskpng_mfp
       // ahead of the loop), hskpng_Tpr, and in fast arithmetic the droplet-independent set-up of the growth rate
       Range r(this, "hskpng_Tpr");
-      // (the last 16 words: the counter of k_cond_lean's list of droplets for the reference's iterates, see cond_list -- cleared with the rest)
       // (two sets of DEFER_SHARDS counters, 64 B apart: the list of droplets for the reference's iterates and the records of the first pass's budget, see cond_list -- cleared here)
       if (fast) { cond_pre.alloc(ncell * sizeof(cond_cell_fast<T>)); defer_cnt.alloc(2 * DEFER_SHARDS * DEFER_CNT_STRIDE); }
       const int n_defer_words = 2 * DEFER_SHARDS * DEFER_CNT_STRIDE;
@@ -1511,144 +1515,90 @@ struct Particles : IParticles {
                          fast ? defer_cnt.p : (uint32_t *)nullptr, fast ? n_defer_words : 0, sstp_fused(step));
       vtpre_valid = false;
     }
+    cond_args<T> a{};
+    cond_listed_pass listed;
+    const dim3 bl(BS);
     if (npart) {
       Range r(this, "cond");
-      cond_args<T> a{sid(), sijk(), A.n.p, A.rd3.p, A.kpa.p, A.vt.p, A.rw2.p, rhod.p, rv.p, Tk.p, eta.p, RH.p,
-                     lambda_D.p, lambda_K.p, m3_before.p, m3_after.p, T(T(dt) / sstp_cond), T(RH_max), eps_tol, T(2.), 100u, step == 0, ncell,
-                     xcd_group(npart, ncell),
-                     turb_cond ? A.ext[ix_ssp].p : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     unsigned(o.dbg_cond_budget > 0 ? std::min(o.dbg_cond_budget, FOLD_CAP) : FOLD_CAP)};
-      const dim3 gr(nblk(npart)), bl(BS);
-      // fast arithmetic: k_cond_lean with the lean bracketed secant, or (opts_init.cond_solver = 1) with TOMS748 -- the reference's
-      // iterates in fast arithmetic; round 2's kernels for that (iteration budget + straggler launch, fold) behind a switch
-      const bool cond_toms = o.cond_solver == 1;
-      if (fast && !cond_toms_two_pass()) {
-        a.pre = reinterpret_cast<const cond_cell_fast<T> *>(cond_pre.p);
-        // the lean solver's list (cond_list): room for every droplet, 8 B each
-        cond_list lst{nullptr, nullptr};
-        bool listed = false;
-        launch_listed = nullptr;               // (a call that threw between the two launches must not leave its second half behind)
-        // round 6: in DEFER_SHARDS parts (one counter each), and the first pass's loop with a budget of trips -- a droplet that needs more
-        // is listed as well (k_cond_lean).  list_parts(): the part's capacity for a launch of `blocks` workgroups of `per_block` droplets
-        auto list_parts = [&](size_t blocks, size_t per_block) {
-          const size_t shard_cap = nblk(blocks, DEFER_SHARDS) * per_block;
-          cond_listed.alloc(2 * size_t(DEFER_SHARDS) * shard_cap);
-          // (the budget: measured and not adopted -- the first pass 3.0 -> 2.75 ms, its second pass 0.26 ms beside the ranking: the step as before)
-          const unsigned budget = !dbg(LCX_DBG_COND_BUDGET) || dbg(LCX_DBG_COND_WQ) ? 100u : o.dbg_cond_budget > 0 && (o.dbg_cond_budget & 255) ? unsigned(o.dbg_cond_budget & 255) : 2u;
-          cond_list l{cond_listed.p, defer_cnt.p, shard_cap, budget, nullptr, nullptr, 0u};
-          if (budget < 100u) {
-            // records for 3 % of the droplets (bench.py's settled boxes leave 1 %; dbg_cond_budget >> 8: a test's own capacity per part)
-            l.rec_cap = o.dbg_cond_budget > 255 ? uint32_t(o.dbg_cond_budget >> 8) : uint32_t(std::max<size_t>(256, shard_cap * 3 / 100));
-            cond_records.alloc(size_t(DEFER_SHARDS) * l.rec_cap * sizeof(lean_record<T>));
-            l.rec = cond_records.p; l.rcount = defer_cnt.p + DEFER_SHARDS * DEFER_CNT_STRIDE;
-          }
-          return l;
-        };
-        const bool want_list = !cond_toms && !dbg(LCX_DBG_COND_NO_LIST);
-        cond_in_storage_order = cond_storage_order;
-        if (cond_in_storage_order) {
-          a.storage_ijk = ijk.p; a.xcd_group = xcd_group(nphys, ncell);
-          if (carry_scatter) { a.sc_rank = rnk(); a.sc_cell_start = cell_start.p; a.sc_sorted_id = sid(); a.sc_sorted_ijk = sijk(); }
-          // (one hygroscopicity in the whole run: a scalar instead of 8 B per droplet, see kpa_uniform)
-          const dim3 gs(nblk(nphys));
-          // (cond_solver = 1: the workgroup folded behind TOMS748's head -- this kernel is bound by instruction issue at half-empty
-          // waves, unlike the lean solver's; LCX_DBG_COND_NO_FOLD: the plain kernel, the same bits)
-          last_cond_kernel = cond_toms ? (dbg(LCX_DBG_COND_NO_FOLD) ? LCX_CK_LEAN_TOMS748 : LCX_CK_FOLD_TOMS748) : dbg(LCX_DBG_COND_LEAN_R3) ? LCX_CK_LEAN_R3 : dbg(LCX_DBG_COND_FOLD) ? LCX_CK_FOLD_LEAN
-                           : dbg(LCX_DBG_COND_WQ) ? LCX_CK_LEAN_WQ : LCX_CK_LEAN;
-          if (cond_toms && !dbg(LCX_DBG_COND_NO_FOLD) && kpa_uniform) hipLaunchKernelGGL((k_cond_lean_fold<T, true, 2>), gs, bl, 0, st, nphys, a, kpa_value);
-          else if (cond_toms && !dbg(LCX_DBG_COND_NO_FOLD)) hipLaunchKernelGGL((k_cond_lean_fold<T, false, 2>), gs, bl, 0, st, nphys, a, T(0));
-          else if (cond_toms && kpa_uniform) hipLaunchKernelGGL((k_cond_lean<T, 15, true, 2>), gs, bl, 0, st, nphys, a, kpa_value);
-          else if (cond_toms) hipLaunchKernelGGL((k_cond_lean<T, 15, false, 2>), gs, bl, 0, st, nphys, a, T(0));
-          else if (dbg(LCX_DBG_COND_LEAN_R3)) hipLaunchKernelGGL((k_cond_lean<T, 11, false, 1>), gs, bl, 0, st, nphys, a, T(0));
-          // (round 5, measured and kept behind a switch: the workgroup folded behind the solver's first loop trip -- the same bits, 6 % fewer
-          // vector instructions per wave at a higher lane use, and not faster: the chip runs this kernel at its package power cap, where
-          // what a launch costs is the lanes that compute, not the instructions that issue; see k_cond_lean_fold)
-          else if (dbg(LCX_DBG_COND_FOLD) && kpa_uniform) hipLaunchKernelGGL((k_cond_lean_fold<T, true>), gs, bl, 0, st, nphys, a, kpa_value);
-          else if (dbg(LCX_DBG_COND_FOLD)) hipLaunchKernelGGL((k_cond_lean_fold<T, false>), gs, bl, 0, st, nphys, a, T(0));
-          else if (!dbg(LCX_DBG_COND_WQ)) {
-            if (dbg(LCX_DBG_COND_PROBE) && kpa_uniform) {      // (measurement only, see k_cond_probe)
-              hipLaunchKernelGGL((k_cond_probe<T, 0>), gs, bl, 0, st, nphys, a, kpa_value); hipLaunchKernelGGL((k_cond_probe<T, 1>), gs, bl, 0, st, nphys, a, kpa_value);
-              hipLaunchKernelGGL((k_cond_probe<T, 2>), gs, bl, 0, st, nphys, a, kpa_value); hipLaunchKernelGGL((k_cond_probe<T, 3>), gs, bl, 0, st, nphys, a, kpa_value);
-              hipLaunchKernelGGL((k_cond_probe<T, 4>), gs, bl, 0, st, nphys, a, kpa_value); hipLaunchKernelGGL((k_cond_probe<T, 5>), gs, bl, 0, st, nphys, a, kpa_value);
-              hipLaunchKernelGGL((k_cond_probe<T, 6>), gs, bl, 0, st, nphys, a, kpa_value);
-            }
-            if (want_list) lst = list_parts(gs.x, BS);
-            if (lst.rec && lst.budget == 2u) {                  // (dbg COND_BUDGET: two trips as straight-line code)
-              if (kpa_uniform) hipLaunchKernelGGL((k_cond_lean<T, 15, true, 0, 2>), gs, bl, 0, st, nphys, a, kpa_value, lst);
-              else hipLaunchKernelGGL((k_cond_lean<T, 15, false, 0, 2>), gs, bl, 0, st, nphys, a, T(0), lst);
-            }
-            else if (lst.rec) {                                 // (any other budget: the run-time form of the loop)
-              if (kpa_uniform) hipLaunchKernelGGL((k_cond_lean<T, 15, true, 0, 0>), gs, bl, 0, st, nphys, a, kpa_value, lst);
-              else hipLaunchKernelGGL((k_cond_lean<T, 15, false, 0, 0>), gs, bl, 0, st, nphys, a, T(0), lst);
-            }
-            else if (kpa_uniform) hipLaunchKernelGGL((k_cond_lean<T, 15, true>), gs, bl, 0, st, nphys, a, kpa_value, lst);
-            else hipLaunchKernelGGL((k_cond_lean<T, 15, false>), gs, bl, 0, st, nphys, a, T(0), lst);
-            listed = lst.ent != nullptr;
-          }
-          else {
-            // round 6: a wave walks n_batch batches of 64 slots and keeps the droplets whose first loop trip has not converged on a queue
-            // of its own in LDS (k_cond_lean_wq: the same bits).  dbg_cond_budget > 0: that many batches (tests, measurements)
-            const unsigned chunks = nblk(nphys);
-            unsigned nb = 8u;
-            while (nb > 1 && chunks / nb < 2048u) nb /= 2;           // (a small box: enough workgroups to fill the device first)
-            if (o.dbg_cond_budget > 0 && (o.dbg_cond_budget & 255)) nb = unsigned(o.dbg_cond_budget & 255);
-            a.xcd_group = std::max(1u, a.xcd_group / nb);
-            const dim3 gw((chunks + nb - 1) / nb);
-            if (want_list) { lst = list_parts(gw.x, size_t(BS) * nb); lst.budget = 100u; }      // (its queue takes the droplets that need more trips)
-            const T kv = kpa_uniform ? kpa_value : T(0);
-            launch_cond_lean_wq<T>(gw, st, wq_params<T>{nphys, a, kv, lst, nb}, kpa_uniform, dbg(LCX_DBG_COND_WQ_CAP128) ? 128 : 96, dbg(LCX_DBG_COND_WQ_PF2) ? 2 : dbg(LCX_DBG_COND_WQ_PF) ? 1 : 0);
-            listed = lst.ent != nullptr;
-          }
-        }
-        else if (cond_toms) { last_cond_kernel = LCX_CK_LEAN_TOMS748_SORTED; hipLaunchKernelGGL((k_cond_lean<T, 15, false, 2>), gr, bl, 0, st, npart, a, T(0)); }
-        else {
-          last_cond_kernel = LCX_CK_LEAN_SORTED;
-          if (want_list) lst = list_parts(gr.x, BS);
-          if (lst.rec) hipLaunchKernelGGL((k_cond_lean<T, 15, false, 0, 0>), gr, bl, 0, st, npart, a, T(0), lst);
-          else hipLaunchKernelGGL((k_cond_lean<T, 15, false>), gr, bl, 0, st, npart, a, T(0), lst);
-          listed = lst.ent != nullptr;
-        }
-        // the listed droplets (brackets that may hold several roots): the reference's iterates, on the same stream ahead of the per-cell
-        // finish -- launched BEHIND the fork of the in-cell ranking below, so that its few thousand waves run next to the ranking's
-        if (listed) {
-          const bool uni = kpa_uniform && cond_in_storage_order;
-          const T kv = uni ? kpa_value : T(0);
-          launch_listed = [this, a, lst, uni, kv, bl]() {
-            // (the host does not know the counts: workgroups for 1 % of the droplets -- the settled boxes list 0.1 %, a swinging one 1 % -- at a droplet per lane,
-            // more droplets by the stride; a workgroup that finds nothing leaves at once)
-            const unsigned per_part = unsigned(std::min<size_t>(2048, std::max<size_t>(8, lst.shard_cap / 100 / BS + 1)));
-            with_bool(uni, [&](auto u) {
-              constexpr bool UNI = decltype(u)::value;
-              if (lst.rec) {
-                const unsigned n_resume = DEFER_SHARDS * ((lst.rec_cap + BS - 1) / BS);
-                hipLaunchKernelGGL((k_cond_lean_resume<T, UNI>), dim3(n_resume), bl, 0, st, a, lst, kv);
-              }
-              hipLaunchKernelGGL((k_cond_lean_listed<T, UNI>), dim3(DEFER_SHARDS * per_part), bl, 0, st, a, lst, kv);
-            });
-          };
-        }
+      a = cond_args<T>{sid(), sijk(), A.n.p, A.rd3.p, A.kpa.p, A.vt.p, A.rw2.p, rhod.p, rv.p, Tk.p, eta.p, RH.p,
+                       lambda_D.p, lambda_K.p, m3_before.p, m3_after.p, T(T(dt) / sstp_cond), T(RH_max), eps_tol, T(2.), 100u, step == 0, ncell,
+                       xcd_group(npart, ncell),
+                       turb_cond ? A.ext[ix_ssp].p : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cbudget.fold_stage()};
+      if (fast) a.pre = reinterpret_cast<const cond_cell_fast<T> *>(cond_pre.p);
+      // the droplets it walks: the sorted order, or the storage -- with the scatter of a sort that was left to it
+      size_t n = npart;
+      if (kp.storage_order) {
+        n = nphys; a.storage_ijk = ijk.p; a.xcd_group = xcd_group(nphys, ncell);
+        if (carry_scatter) { a.sc_rank = rnk(); a.sc_cell_start = cell_start.p; a.sc_sorted_id = sid(); a.sc_sorted_ijk = sijk(); }
       }
-      else if (fast) {
-        a.pre = reinterpret_cast<const cond_cell_fast<T> *>(cond_pre.p);
-        // two passes: a short iteration budget first, the droplets that need more in a dense second launch (k_cond_fast)
-        // The second launch costs what its slowest wave costs (~60 us) however few droplets it holds, and the first pass saves ~2.3 us
-        // per million droplets: one pass below 2^25 droplets (a 16-plane slab of C3, 16.7e6 SDs: 0.96 ms in two passes, 0.91 in one).
-        // opts_init.dbg_cond_budget: test / measurement switch (the parity tests force the two-pass form at their small sizes with it)
-        const int budget = o.dbg_cond_budget > 0 ? o.dbg_cond_budget : o.dbg_cond_budget < 0 ? 0 : (npart >= (size_t(1) << 25) ? 6 : 0);
-        // (`rank` is free between the sorts; part s holds at most the positions of the workgroups b with b % DEFER_SHARDS == s)
-        cond_defer df{rnk(), defer_cnt.p, size_t(nblk(nblk(npart), DEFER_SHARDS)) * BS, unsigned(budget)};
-        if (size_t(DEFER_SHARDS) * df.shard_cap > cap) df.budget = 0;           // (tiny set-ups: the parts do not fit the scratch)
-        const bool fold = !dbg(LCX_DBG_COND_NO_FOLD);                             // (test / measurement switch)
-        last_cond_kernel = LCX_CK_TOMS748_TWO_PASS;
-        if (fold) hipLaunchKernelGGL((k_cond_fast_fold<T, 11>), gr, bl, 0, st, npart, a, df);
-        else hipLaunchKernelGGL((k_cond_fast<T, 11, false>), gr, bl, 0, st, npart, a, df);
-        if (df.budget) {
-          const unsigned per_shard = std::max(1u, std::min(nblk(npart / 8 + 1), 256u * 64u) / DEFER_SHARDS);
-          hipLaunchKernelGGL((k_cond_fast<T, 11, true>), dim3(per_shard * DEFER_SHARDS), bl, 0, st, npart, a, df);
+      const dim3 g(nblk(n));
+      // (one hygroscopicity in the whole run: a scalar instead of 8 B per droplet, see kpa_uniform)
+      const T kv = kp.uni ? kpa_value : T(0);
+      // the lean solver's list (cond_list): room for every droplet, 8 B each, in DEFER_SHARDS parts (one counter each) for a launch of
+      // `blocks` workgroups of `per_block` droplets; round 6: the first pass's loop with a budget of trips -- a droplet that needs more
+      // leaves a record (k_cond_lean)
+      auto make_list = [&](size_t blocks, size_t per_block) {
+        if (!kp.want_list) return;
+        const size_t shard_cap = cond_list_shard_cap(blocks, per_block, DEFER_SHARDS);
+        cond_listed.alloc(2 * size_t(DEFER_SHARDS) * shard_cap);
+        cond_list &l = listed.lst;
+        l = cond_list{cond_listed.p, defer_cnt.p, shard_cap, kp.trips, nullptr, nullptr, 0u};
+        if (kp.budget != cond_budget_form::NONE) {
+          l.rec_cap = cbudget.records_per_part(shard_cap);
+          cond_records.alloc(size_t(DEFER_SHARDS) * l.rec_cap * sizeof(lean_record<T>));
+          l.rec = cond_records.p; l.rcount = defer_cnt.p + DEFER_SHARDS * DEFER_CNT_STRIDE;
+          listed.n_resume = cond_resume_grid(l.rec_cap, BS, DEFER_SHARDS);
         }
+        listed.on = true; listed.uni = kp.uni; listed.kv = kv; listed.per_part = cond_listed_per_part(shard_cap, BS);
+      };
+      last_cond_kernel = kp.kernel;
+      switch (kp.kernel) {
+      case LCX_CK_STRICT: hipLaunchKernelGGL((k_cond<T, false>), g, bl, 0, st, npart, a); break;
+      case LCX_CK_FAST_PER_DROPLET_SETUP: hipLaunchKernelGGL((k_cond<T, true>), g, bl, 0, st, npart, a); break;
+      case LCX_CK_TOMS748_TWO_PASS: {
+        cond_defer df{rnk(), defer_cnt.p, cond_two_pass_shard_cap(npart, BS, DEFER_SHARDS), cond_two_pass_budget(cbudget, npart, BS, DEFER_SHARDS, cap)};
+        if (!ctg.no_fold) hipLaunchKernelGGL((k_cond_fast_fold<T, 11>), g, bl, 0, st, npart, a, df);
+        else hipLaunchKernelGGL((k_cond_fast<T, 11, false>), g, bl, 0, st, npart, a, df);
+        if (df.budget) hipLaunchKernelGGL((k_cond_fast<T, 11, true>), dim3(cond_two_pass_per_shard(npart, BS, DEFER_SHARDS) * DEFER_SHARDS), bl, 0, st, npart, a, df);
+        break;
       }
-      else if (o.strict_fp) { last_cond_kernel = LCX_CK_STRICT; hipLaunchKernelGGL((k_cond<T, false>), gr, bl, 0, st, npart, a); }
-      else { last_cond_kernel = LCX_CK_FAST_PER_DROPLET_SETUP; hipLaunchKernelGGL((k_cond<T, true>), gr, bl, 0, st, npart, a); }
+      case LCX_CK_FOLD_TOMS748: with_bool(kp.uni, [&](auto u) { hipLaunchKernelGGL((k_cond_lean_fold<T, decltype(u)::value, 2>), g, bl, 0, st, n, a, kv); }); break;
+      case LCX_CK_LEAN_TOMS748: with_bool(kp.uni, [&](auto u) { hipLaunchKernelGGL((k_cond_lean<T, 15, decltype(u)::value, 2>), g, bl, 0, st, n, a, kv); }); break;
+      case LCX_CK_LEAN_TOMS748_SORTED: hipLaunchKernelGGL((k_cond_lean<T, 15, false, 2>), g, bl, 0, st, n, a, T(0)); break;
+      case LCX_CK_LEAN_R3: hipLaunchKernelGGL((k_cond_lean<T, 11, false, 1>), g, bl, 0, st, n, a, T(0)); break;
+      case LCX_CK_FOLD_LEAN: with_bool(kp.uni, [&](auto u) { hipLaunchKernelGGL((k_cond_lean_fold<T, decltype(u)::value>), g, bl, 0, st, n, a, kv); }); break;
+      case LCX_CK_LEAN_WQ: {
+        const unsigned chunks = nblk(nphys), nb = cbudget.wq_batches(chunks);
+        a.xcd_group = std::max(1u, a.xcd_group / nb);
+        const dim3 gw(cond_wq_grid(chunks, nb));
+        make_list(gw.x, size_t(BS) * nb);
+        launch_cond_lean_wq<T>(gw, st, wq_params<T>{nphys, a, kv, listed.lst, nb}, kp.uni, ctg.wq_cap(), ctg.wq_prefetch());
+        break;
+      }
+      case LCX_CK_LEAN:
+        if (kp.probe) {                                      // (measurement only, see k_cond_probe)
+          hipLaunchKernelGGL((k_cond_probe<T, 0>), g, bl, 0, st, n, a, kv); hipLaunchKernelGGL((k_cond_probe<T, 1>), g, bl, 0, st, n, a, kv);
+          hipLaunchKernelGGL((k_cond_probe<T, 2>), g, bl, 0, st, n, a, kv); hipLaunchKernelGGL((k_cond_probe<T, 3>), g, bl, 0, st, n, a, kv);
+          hipLaunchKernelGGL((k_cond_probe<T, 4>), g, bl, 0, st, n, a, kv); hipLaunchKernelGGL((k_cond_probe<T, 5>), g, bl, 0, st, n, a, kv);
+          hipLaunchKernelGGL((k_cond_probe<T, 6>), g, bl, 0, st, n, a, kv);
+        }
+        make_list(g.x, BS);
+        with_bool(kp.uni, [&](auto u) {
+          constexpr bool UNI = decltype(u)::value;
+          switch (kp.budget) {
+          case cond_budget_form::TWO: hipLaunchKernelGGL((k_cond_lean<T, 15, UNI, 0, 2>), g, bl, 0, st, n, a, kv, listed.lst); break;
+          case cond_budget_form::RUN_TIME: hipLaunchKernelGGL((k_cond_lean<T, 15, UNI, 0, 0>), g, bl, 0, st, n, a, kv, listed.lst); break;
+          case cond_budget_form::NONE: hipLaunchKernelGGL((k_cond_lean<T, 15, UNI>), g, bl, 0, st, n, a, kv, listed.lst); break;
+          }
+        });
+        break;
+      case LCX_CK_LEAN_SORTED:
+        make_list(g.x, BS);
+        if (kp.budget == cond_budget_form::RUN_TIME) hipLaunchKernelGGL((k_cond_lean<T, 15, false, 0, 0>), g, bl, 0, st, n, a, T(0), listed.lst);
+        else hipLaunchKernelGGL((k_cond_lean<T, 15, false>), g, bl, 0, st, n, a, T(0), listed.lst);
+        break;
+      default: throw lcx_error("cond_substep: not a per-substep kernel");      // (LCX_CK_PER_PARTICLE, LCX_CK_SUBSTEPS: the other two routes)
+      }
     }
     if (carry_scatter) {                                      // the in-cell ranking, behind the kernel that scattered
       // (on its own stream when the list of crowded cells is on the host already, i.e. nothing in it waits for the device)
@@ -1672,13 +1622,21 @@ struct Particles : IParticles {
         rank_pending = true;
       } else finish_deferred_sort(true);
     }
+    // the listed droplets, on the same stream ahead of the per-cell finish -- launched BEHIND the fork of the in-cell ranking above, so
+    // that its few thousand waves run next to the ranking's
     // ("cond_listed": a stage of its own since round 6 -- "cond" is the first pass's kernel alone, what the roofline prices)
-    if (launch_listed) { Range r(this, "cond_listed"); launch_listed(); launch_listed = nullptr; }
+    if (listed.on) {
+      Range r(this, "cond_listed");
+      with_bool(listed.uni, [&](auto u) {
+        constexpr bool UNI = decltype(u)::value;
+        if (listed.lst.rec) hipLaunchKernelGGL((k_cond_lean_resume<T, UNI>), dim3(listed.n_resume), bl, 0, st, a, listed.lst, listed.kv);
+        hipLaunchKernelGGL((k_cond_lean_listed<T, UNI>), dim3(DEFER_SHARDS * listed.per_part), bl, 0, st, a, listed.lst, listed.kv);
+      });
+    }
     {
       Range r(this, "cond_cellfinish");
       // (a kernel that carried the scatter has left each droplet's change at the droplet's place in the sorted order: no gather)
-      launch_cellfinish(step, sstp_cond, fast, cond_in_storage_order && !carry_scatter ? sid() : (const uint32_t *)nullptr);
-      cond_in_storage_order = false;
+      launch_cellfinish(step, sstp_cond, fast, npart && kp.storage_order && !carry_scatter ? sid() : (const uint32_t *)nullptr);
     }
   }
   // every super-droplet of the run carries the same hygroscopicity: one dry distribution (or one (kappa, rd_insol) key of dry_sizes),
@@ -1686,27 +1644,33 @@ struct Particles : IParticles {
   // a scalar.  (LCX_DBG_KPA_ARRAY: the array is read all the same.)
   bool kpa_uniform = false; T kpa_value = T(0);
   int last_cond_kernel = 0;                  // (enum lcx_cond_kernel of the last condensation launch: "raw_mode")
-  std::function<void()> launch_listed;       // (cond_substep: k_cond_lean_listed, queued behind the fork of the in-cell ranking)
-  const bool cond_storage_order = !dbg(LCX_DBG_COND_SORTED_ORDER);      // (measurement switch: the positional form)
-  bool cond_in_storage_order = false;
-  // per-cell sums of n rw^3 before / after the substep + update_th_rv.  Strict arithmetic: the ordered single-lane walk (the
-  // reference's summation order); fast: eight lanes per cell, or a whole wave per cell where cells are crowded
+  lcx_cond_finish last_cond_finish = LCX_CF_NONE;      // (of the last per-cell finish: "raw_cond_finish"; no part of a snapshot)
+  // the per-cell finish in the form that cond_finish_of names (lcx_cond_plan.hpp)
   void launch_cellfinish(int step, int sstp, bool delta = false, const uint32_t *gather = nullptr)
   {
     const int dl = delta ? 1 : 0;
-    if (!o.strict_fp && ncell >= 4096 && npart / ncell >= 192)
+    last_cond_finish = cond_finish_of(o.strict_fp != 0, delta, gather != nullptr, ctg.finish_staged, ncell, npart);
+    switch (last_cond_finish) {
+    case LCX_CF_WAVE:
       hipLaunchKernelGGL(k_cond_cellfinish_wave<T>, dim3(nblk(ncell, BS / WAVE)), dim3(BS), 0, st, ncell, cell_start.p, m3_before.p, m3_after.p, dv.p, rhod.p,
                          rv.p, th.p, Tk.p, rw_mom3.p, step, sstp, n_dims, dl, gather);
-    else if (!o.strict_fp && delta && !gather && !dbg(LCX_DBG_FINISH_STAGED))
+      break;
+    case LCX_CF_DIRECT:
       hipLaunchKernelGGL(k_cond_cellfinish_direct<T>, dim3(nblk(ncell * 8)), dim3(BS), 0, st, ncell, cell_start.p, m3_after.p, dv.p, rhod.p, rv.p, th.p, Tk.p,
                          rw_mom3.p, n_dims);
-    else if (!o.strict_fp) {
+      break;
+    case LCX_CF_LANES8: {
       const int cfc = std::min(cf_cells(), BS / 8);
       hipLaunchKernelGGL((k_cond_cellfinish<T, 8>), dim3(nblk(ncell, cfc)), dim3(BS), 0, st, ncell, cfc, cell_start.p, m3_before.p, m3_after.p, dv.p, rhod.p,
                          rv.p, th.p, Tk.p, rw_mom3.p, step, sstp, n_dims, dl, gather);
-    } else
+      break;
+    }
+    case LCX_CF_ORDERED:
       hipLaunchKernelGGL((k_cond_cellfinish<T, 1>), dim3(nblk(ncell, cf_cells())), dim3(BS), 0, st, ncell, cf_cells(), cell_start.p, m3_before.p, m3_after.p, dv.p, rhod.p,
                          rv.p, th.p, Tk.p, rw_mom3.p, step, sstp, n_dims, dl, gather);
+      break;
+    case LCX_CF_NONE: break;
+    }
   }
   // hskpng_rc2.ipp:14-32
   void hskpng_approximate_rc2_invalid()
@@ -3315,13 +3279,11 @@ struct Particles : IParticles {
     if (opts.cond) {
       if (cdr.on) cdr_before();                    // (include/lcx_cond_rates.h: rw2 as stored ahead of the first condensation launch)
       if (trb_on) trb_begin<TRB_COND>();           // (include/lcx_track_budget.h: the tracked droplets' rw2 ahead of it)
-      // (a measurement switch that names one of the per-substep kernels gets that kernel)
-      constexpr unsigned per_substep_variants = LCX_DBG_COND_NO_FUSED_SUBSTEPS | LCX_DBG_COND_FOLD | LCX_DBG_COND_WQ | LCX_DBG_COND_BUDGET | LCX_DBG_COND_PROBE |
-                                                LCX_DBG_COND_LEAN_R3 | LCX_DBG_FINISH_STAGED | LCX_DBG_COND_NO_FOLD;
-      const bool fused_substeps = sstp_cond > 1 && lean_storage_cond() && !opts.turb_cond && npart && !(o.dbg_flags & per_substep_variants);
-      if (fused_substeps || !(sort_deferred && lean_storage_cond() && !opts.turb_cond && !(o.exact_sstp_cond && (sstp_cond > 1 || sstp_cond_act > 1)))) hskpng_sort();
-      if (o.exact_sstp_cond && (sstp_cond > 1 || sstp_cond_act > 1)) { hskpng_mfp(); cond_perparticle(opts.RH_max, opts.turb_cond); }
-      else if (fused_substeps) cond_substeps_fused(opts.RH_max);
+      // which route (lcx_cond_plan.hpp), and whether the sort is made ahead of it or its first kernel carries the scatter
+      const cond_route_plan rt = cond_route_of(ctg, sstp_cond, sstp_cond_act, sort_deferred, opts.turb_cond, npart);
+      if (rt.sort_ahead) hskpng_sort();
+      if (rt.route == cond_route::PER_PARTICLE) { hskpng_mfp(); cond_perparticle(opts.RH_max, opts.turb_cond); }
+      else if (rt.route == cond_route::SUBSTEPS_FUSED) cond_substeps_fused(opts.RH_max);
       else for (int step = 0; step < sstp_cond; ++step) {
         // (the Eulerian fields' substep rides on the cell pass of cond_substep: sstp_fused)
         if (opts.turb_cond && nphys)                                                     // apply_perparticle_sgs_supersat.ipp
@@ -3654,6 +3616,7 @@ struct Particles : IParticles {
     else if (s == "raw_mode") {                    // what this object runs: strict_fp, cond_solver, the kernel of its last condensation launch (enum lcx_cond_kernel), dbg_flags
       v = {(unsigned long long)(o.strict_fp ? 1 : 0), (unsigned long long)o.cond_solver, (unsigned long long)last_cond_kernel, (unsigned long long)o.dbg_flags};
     }
+    else if (s == "raw_cond_finish") v.assign(1, (unsigned long long)last_cond_finish);      // the form of its last per-cell finish (enum lcx_cond_finish)
     else if (s == "raw_coal_ranked") v.assign(1, (unsigned long long)last_coal_ranked);
     else if (s == "raw_coal_skip") {               // launches of the last step_async that used a bound; LCX_DBG2_COAL_SKIP_COUNT: + pairs skipped, pairs examined
       v.assign(1, (unsigned long long)last_coal_skip);
@@ -3950,7 +3913,7 @@ struct Particles : IParticles {
   {
     const int every_ = o.reorder_every > 0 ? o.reorder_every : SLAB_REORDER_EVERY;
     const bool reorder_sched = !strict_order() && steps_since_reorder + 1 >= every_;
-    return defer_sort_ok && lean_storage_cond() && !reorder_sched && replay.empty() && !dbg(LCX_DBG_EXCH_SORT_NOW);
+    return defer_sort_ok && ctg.lean_storage() && !reorder_sched && replay.empty() && !dbg(LCX_DBG_EXCH_SORT_NOW);
   }
   bool overlap_possible() const
   { return dev_exchange && !no_overlap && fused_pending && n_dims > 0 && o.nx > 2 * bnd_planes() && sort_headroom > 0 && nphys > 0 && !sort_will_be_deferred(); }

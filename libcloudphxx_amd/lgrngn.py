@@ -157,6 +157,15 @@ class cond_kernel(enum.IntEnum):
     substeps = 13
 
 
+class cond_finish(enum.IntEnum):
+    """enum lcx_cond_finish (include/lcx.h): the form of an object's last per-cell finish, state_u64("raw_cond_finish")"""
+    none = 0
+    ordered = 1
+    lanes8 = 2
+    direct = 3
+    wave = 4
+
+
 class src_t(_bp_enum):              # lgrngn/ccn_source.hpp:8
     off = 0
     simple = 1
