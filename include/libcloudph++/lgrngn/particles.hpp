@@ -23,6 +23,7 @@
 #include "../../lcx_track.h"
 #include "../../lcx_track_budget.h"
 #include "../../lcx_dump.h"
+#include "../../lcx_coal_log.h"
 
 namespace libcloudphxx { namespace lgrngn {
   namespace chem = common::chem;
@@ -176,6 +177,14 @@ namespace libcloudphxx { namespace lgrngn {
   {
     acnv_m3 = LCX_CR_ACNV_M3, acnv_nc = LCX_CR_ACNV_NC, acnv_nr = LCX_CR_ACNV_NR, accr_m3 = LCX_CR_ACCR_M3, accr_nc = LCX_CR_ACCR_NC,
     self_cloud_n = LCX_CR_SELF_CLOUD_N, self_rain_n = LCX_CR_SELF_RAIN_N, count = LCX_CR_COUNT
+  };
+
+  // the rows of particles_t<real_t, HIP>::coal_log (an extension without a reference counterpart; include/lcx_coal_log.h defines each)
+  enum class coal_log_field_t : int
+  {
+    launch = LCX_CLG_LAUNCH, cell = LCX_CLG_CELL, slot_d = LCX_CLG_SLOT_D, slot_r = LCX_CLG_SLOT_R, col_no = LCX_CLG_COL_NO, n_d = LCX_CLG_N_D,
+    n_r = LCX_CLG_N_R, rw2_d = LCX_CLG_RW2_D, rw2_r = LCX_CLG_RW2_R, rw2_new = LCX_CLG_RW2_NEW, rd3_d = LCX_CLG_RD3_D, rd3_r = LCX_CLG_RD3_R,
+    vt_d = LCX_CLG_VT_D, vt_r = LCX_CLG_VT_R, count = LCX_CLG_FIELDS
   };
 
   namespace detail
@@ -559,6 +568,34 @@ namespace libcloudphxx { namespace lgrngn {
       if (n_qualifying) *n_qualifying = Q;
       std::vector<std::vector<double>> out(f.size());
       for (size_t k = 0; k < f.size(); ++k) out[k].assign(flat.begin() + k * max_count, flat.begin() + k * max_count + written);
+      return out;
+    }
+    // EXTENSION, no reference counterpart (include/lcx_coal_log.h): every coalescence event -- the two droplets, their sizes and
+    // multiplicities before it, the collision count, the product -- appended to a list of `capacity` events on the device by the
+    // coalescence kernels while enabled; r_min > 0 keeps the events whose product has a wet radius of at least r_min.  coal_log: one
+    // vector per coal_log_field_t, each of `held` elements, in no particular order; reset empties the log behind the read.  A snapshot
+    // does not hold it: a restored object has it disabled.  Not virtual: particles_proto_t stays the reference's.
+    struct coal_log_info_t { bool enabled; size_t capacity; double r_min; unsigned long long held, seen, launches; };
+    void coal_log_enable(size_t capacity, real_t r_min = 0) { detail::lcx_check(lcx_coal_log_enable(pimpl->h, capacity, double(r_min))); }
+    void coal_log_disable() { detail::lcx_check(lcx_coal_log_disable(pimpl->h)); }
+    coal_log_info_t coal_log_info()
+    {
+      int en = 0;
+      coal_log_info_t i{};
+      detail::lcx_check(lcx_coal_log_info(pimpl->h, &en, &i.capacity, &i.r_min, &i.held, &i.seen, &i.launches));
+      i.enabled = en != 0;
+      return i;
+    }
+    std::vector<std::vector<double>> coal_log(bool reset = false)
+    {
+      unsigned long long held = 0;
+      detail::lcx_check(lcx_coal_log_info(pimpl->h, nullptr, nullptr, nullptr, &held, nullptr, nullptr));
+      const size_t room = std::max<size_t>(size_t(held), 1);
+      size_t written = 0;
+      std::vector<double> flat(size_t(LCX_CLG_FIELDS) * room);
+      detail::lcx_check(lcx_coal_log_read(pimpl->h, flat.data(), room, room, 0, reset ? 1 : 0, &written, nullptr));
+      std::vector<std::vector<double>> out(LCX_CLG_FIELDS);
+      for (size_t k = 0; k < size_t(LCX_CLG_FIELDS); ++k) out[k].assign(flat.begin() + k * room, flat.begin() + k * room + written);
       return out;
     }
 

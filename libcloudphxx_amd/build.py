@@ -13,13 +13,14 @@ OUT = os.path.join(CSRC, "liblcx_hip.so")
 # loop-invariant code motion (csrc/lcx_cond_wq.hpp says why); everything else with the compiler's defaults.
 SRCS = [("lcx_core.hip", []), ("lcx_cond_wq.hip", ["-mllvm", "-disable-machine-licm"])]
 DEPS = ["lcx_core.hip", "lcx_cond_wq.hip", "lcx_cond_wq.hpp", "lcx_kernels.hpp", "lcx_math.hpp", "lcx_multi.hpp", "lcx_pool.hpp",
-        "lcx_snapshot_format.hpp", "lcx_snapshot_kernels.hpp", "lcx_diag_plan.hpp", "lcx_coal_prevote.hpp", "lcx_coal_plan.hpp", "lcx_cond_plan.hpp", "lcx_coal_floor_probe.h", "lcx_track_plan.hpp", "lcx_dump_plan.hpp",
+        "lcx_snapshot_format.hpp", "lcx_snapshot_kernels.hpp", "lcx_diag_plan.hpp", "lcx_coal_prevote.hpp", "lcx_coal_plan.hpp", "lcx_cond_plan.hpp", "lcx_coal_floor_probe.h", "lcx_track_plan.hpp", "lcx_dump_plan.hpp", "lcx_coal_log_plan.hpp",
         os.path.join("..", "..", "include", "lcx.h"), os.path.join("..", "..", "include", "lcx_rlx.h"),
         os.path.join("..", "..", "include", "lcx_chem.h"), os.path.join("..", "..", "include", "lcx_state.h"),
         os.path.join("..", "..", "include", "lcx_diag.h"), os.path.join("..", "..", "include", "lcx_coal_rates.h"),
         os.path.join("..", "..", "include", "lcx_cond_rates.h"),
         os.path.join("..", "..", "include", "lcx_move_rates.h"), os.path.join("..", "..", "include", "lcx_track.h"),
-        os.path.join("..", "..", "include", "lcx_track_budget.h"), os.path.join("..", "..", "include", "lcx_dump.h")]
+        os.path.join("..", "..", "include", "lcx_track_budget.h"), os.path.join("..", "..", "include", "lcx_dump.h"),
+        os.path.join("..", "..", "include", "lcx_coal_log.h")]
 
 
 def needs_build():

@@ -34,6 +34,7 @@
 #include "../../include/lcx_track.h"
 #include "../../include/lcx_track_budget.h"
 #include "../../include/lcx_dump.h"
+#include "../../include/lcx_coal_log.h"
 #include "lcx_kernels.hpp"
 #include "lcx_snapshot_kernels.hpp"
 #include "lcx_pool.hpp"
@@ -157,6 +158,11 @@ struct IParticles {
   virtual void coal_rates_info(int *, double *, unsigned long long *) { not_built("coal_rates"); }
   virtual void coal_rates_read(double *, size_t, bool, bool) { not_built("coal_rates"); }
   virtual void diag_coal_rate(int) { not_built("coal_rates"); }
+  // the collision log (include/lcx_coal_log.h): built for a single-device object
+  virtual void coal_log_enable(size_t, double) { not_built("coal_log"); }
+  virtual void coal_log_disable() { not_built("coal_log"); }
+  virtual void coal_log_info(int *, size_t *, double *, unsigned long long *, unsigned long long *, unsigned long long *) { not_built("coal_log"); }
+  virtual void coal_log_read(double *, size_t, size_t, bool, bool, size_t *, unsigned long long *) { not_built("coal_log"); }
   // condensation rates per cell (include/lcx_cond_rates.h): built for a single-device object
   virtual void cond_rates_enable(const double *, int) { not_built("cond_rates"); }
   virtual void cond_rates_disable() { not_built("cond_rates"); }
@@ -1879,10 +1885,74 @@ struct Particles : IParticles {
   // one that cannot collide); off, nothing below is looked at and every launch is the one it was.
   RateTable cr{"coal_rates", "the accumulators are"};
   static constexpr uint64_t CR_N_ROWS = ((1ull << LCX_CR_COUNT) - 1) & ~((1ull << LCX_CR_ACNV_M3) | (1ull << LCX_CR_ACCR_M3));
-  coal_tally_arg<T, true> cr_arg()                  // what a tallying launch is handed; counts the launch ("launches" of lcx_coal_rates_info)
+  // what a launch of a TALLY form is handed -- the accumulators where the rates are on, the list where the log is -- and counts the launch for
+  // each that is ("launches" of lcx_coal_rates_info and of lcx_coal_log_info)
+  coal_tally_arg<T, true> tally_arg()
   {
-    ++cr.calls;
-    return coal_tally_arg<T, true>{cr.acc.p, ncell, rt_lo(cr.r_thr[0])};
+    coal_tally_arg<T, true> ta{nullptr, ncell, T(0), nullptr, 0, nullptr, T(0), 0};
+    if (cr.on) { ++cr.calls; ta.acc = cr.acc.p; ta.lo = rt_lo(cr.r_thr[0]); }
+    if (clog.on) { ta.log = clog.list.p; ta.log_cap = clog.cap; ta.log_cur = clog.cur.p; ta.log_lo = rt_lo(clog.r_min); ta.log_launch = clog.launches++; }
+    return ta;
+  }
+  // ---- the collision log (include/lcx_coal_log.h): every event of the TALLY forms appended to one list; lcx_coal_log_plan.hpp has the rules ----
+  // list is [LCX_CLG_FIELDS][cap] words; cur[0] is the cursor that the kernels add to (`seen`), cur[1] its value as the last read saw it.
+  struct CoalLog {
+    bool on = false; size_t cap = 0; double r_min = 0; unsigned long long launches = 0;
+    DevBuf<unsigned long long> list, cur; DevBuf<double> out; std::vector<double> host;    // (out, host: a host read's staging on the device and on the host)
+  } clog;
+  void coal_log_enable(size_t capacity, double r_min) override
+  {
+    std::string err;
+    if (!coal_log::validate(capacity, r_min, err)) throw lcx_error(err);
+    // the new list first, by hand: a refusal names the bytes and leaves the object as it was
+    unsigned long long *list = nullptr, *cur = nullptr;
+    const size_t n_bytes = coal_log::bytes(capacity);
+    hipError_t e = hipMalloc((void **)&list, n_bytes);
+    if (e == hipSuccess && (e = hipMalloc((void **)&cur, 2 * sizeof(unsigned long long))) != hipSuccess) (void)hipFree(list);
+    if (e != hipSuccess) { (void)hipGetLastError(); throw lcx_error(coal_log::alloc_failed(n_bytes, hipGetErrorString(e))); }
+    if (clog.list.p) HIPCHK(hipStreamSynchronize(st));                  // (a kernel still queued may append to the list that is freed)
+    clog.list.release(); clog.cur.release(); clog.out.release();
+    clog.list.p = list; clog.list.n = coal_log::words(capacity); clog.cur.p = cur; clog.cur.n = 2;
+    clog.on = true; clog.cap = capacity; clog.r_min = r_min; clog.launches = 0;
+    HIPCHK(hipMemsetAsync(clog.cur.p, 0, 2 * sizeof(unsigned long long), st));
+  }
+  void coal_log_disable() override
+  {
+    clog.on = false; clog.cap = 0; clog.r_min = 0; clog.launches = 0;
+    if (clog.list.p) { HIPCHK(hipStreamSynchronize(st)); clog.list.release(); clog.cur.release(); clog.out.release(); }
+  }
+  void coal_log_info(int *enabled, size_t *capacity, double *r_min, unsigned long long *held, unsigned long long *seen, unsigned long long *launches) override
+  {
+    unsigned long long s = 0;
+    if (clog.on && (held || seen)) { HIPCHK(hipMemcpyAsync(&s, clog.cur.p, sizeof s, hipMemcpyDeviceToHost, st)); sync(); }
+    if (enabled) *enabled = clog.on ? 1 : 0;
+    if (capacity) *capacity = clog.cap;
+    if (r_min) *r_min = clog.r_min;
+    if (held) *held = coal_log::held(s, clog.cap);
+    if (seen) *seen = s;
+    if (launches) *launches = clog.launches;
+  }
+  // on the stream: the conversion (all held events, or none where they do not fit), the cursor's copy and the reset behind it, the copies to the
+  // host; one wait.  Whether the events fitted is known only behind it: the kernels have applied lcx_coal_log_plan.hpp's rule themselves
+  void coal_log_read(double *out, size_t field_stride, size_t cap_events, bool on_device, bool reset, size_t *n_written, unsigned long long *seen) override
+  {
+    std::string err;
+    if (!clog.on) throw lcx_error(coal_log::not_enabled("read"));
+    if (!coal_log::validate_out(out, field_stride, cap_events, err)) throw lcx_error(err);
+    const size_t m = std::min(cap_events, clog.cap);
+    if (!on_device) { clog.out.alloc(size_t(LCX_CLG_FIELDS) * m); clog.host.resize(size_t(LCX_CLG_FIELDS) * m); }
+    if (m) hipLaunchKernelGGL(k_coal_log_f64, dim3(nblk(m), LCX_CLG_FIELDS), dim3(BS), 0, st, (const unsigned long long *)clog.list.p, clog.cap,
+                              (const unsigned long long *)clog.cur.p, cap_events, on_device ? out : clog.out.p, on_device ? field_stride : m);
+    hipLaunchKernelGGL(k_coal_log_finish, dim3(1), dim3(WAVE), 0, st, clog.cur.p, clog.cap, cap_events, int(reset));
+    unsigned long long s = 0;
+    HIPCHK(hipMemcpyAsync(&s, clog.cur.p + 1, sizeof s, hipMemcpyDeviceToHost, st));
+    if (!on_device && m) HIPCHK(hipMemcpyAsync(clog.host.data(), clog.out.p, clog.host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    sync();
+    if (!coal_log::validate_room(s, clog.cap, cap_events, err)) throw lcx_error(err);
+    const size_t held = size_t(coal_log::held(s, clog.cap));
+    if (!on_device) for (int f = 0; f < LCX_CLG_FIELDS; ++f) memcpy(out + size_t(f) * field_stride, clog.host.data() + size_t(f) * m, held * sizeof(double));
+    if (n_written) *n_written = held;
+    if (seen) *seen = s;
   }
   void coal_rates_enable(double r_thr) override
   {
@@ -2432,10 +2502,10 @@ struct Particles : IParticles {
       }
       // (with a bound: the form whose workgroups leave ahead of the ranking where they keep no pair; LCX_DBG2_NO_COAL_RANK_EXIT, or the last
       // counters showed too few leaving: round 8's form.  With the collision rates on: the same form, tallying)
-      with_bool(coal_marks_dead, cr.on, [&](auto mark, auto tallies) {
+      with_bool(coal_marks_dead, cr.on || clog.on, [&](auto mark, auto tallies) {        // (the collision log rides the same form)
         constexpr bool MK = decltype(mark)::value, TL = decltype(tallies)::value;
         coal_tally_arg<T, TL> ta{};
-        if constexpr (TL) ta = cr_arg();
+        if constexpr (TL) ta = tally_arg();
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, gr, dim3(BS), 0, st, npart, (const uint32_t *)(sorted_id.p + sort_base), (const uint32_t *)sijk(), (const uint32_t *)cell_start.p,
                              deferred_rs, A.n.p, A.rw2.p, A.vt.p, A.rd3.p, (const T *)dv.p, T(dt_sub), kc, rs, coal_marks_dead ? ijk.p : nullptr, ska, ta);
@@ -2468,10 +2538,10 @@ struct Particles : IParticles {
     const bool kappa_pass = o.n_dry_distros + n_size_keys > 1, chem_pass = o.chem_switch != 0;
     const bool tabulated = o.kernel != LCX_KERNEL_GOLOVIN && o.kernel != LCX_KERNEL_GEOMETRIC && o.kernel != LCX_KERNEL_LONG;
     const bool production = tabulated && !pure_const_multi && !rs.arr && !use_rc2 && ix_ict < 0 && coal_marks_dead;
-    with_bool(cr.on, [&](auto tallies) {                  // (with the collision rates on: the same three kernels, feeding their accumulators)
+    with_bool(cr.on || clog.on, [&](auto tallies) {       // (with the collision rates or the log on: the same three kernels, feeding them)
       constexpr bool TL = decltype(tallies)::value;
       coal_tally_arg<T, TL> ta{};
-      if constexpr (TL) ta = cr_arg();
+      if constexpr (TL) ta = tally_arg();
       auto launch = [&](auto kern, bool need_col = true) {
         hipLaunchKernelGGL(kern, dim3(nblk((npart + 1) / 2)), dim3(BS), 0, st, npart, sid(), sijk(), cell_start.p, A.n.p, A.rw2.p, A.vt.p,
                            A.rd3.p, need_col ? col.p : (T *)nullptr, dv.p, T(dt_sub), kc, rs, int(pure_const_multi), d_flag.p, use_rc2 ? A.ext[ix_rc2].p : nullptr,
@@ -4481,6 +4551,7 @@ struct Particles : IParticles {
       coal_rates_disable();                        // (include/lcx_coal_rates.h: no snapshot holds the accumulators, a restored object starts without them)
       cond_rates_disable();                        // (include/lcx_cond_rates.h: the same)
       move_rates_disable();                        // (include/lcx_move_rates.h: the same)
+      coal_log_disable();                          // (include/lcx_coal_log.h: the same)
       if (ix_trk >= 0) track_disable();            // (include/lcx_track.h: the same)
     } catch (...) { roll_back(); throw; }
   }
@@ -4766,6 +4837,20 @@ int lcx_coal_rates_disable(lcx_particles *h) { LCX_TRY(H->coal_rates_disable()) 
 int lcx_coal_rates_info(lcx_particles *h, int *enabled, double *r_thr, unsigned long long *launches) { LCX_TRY(H->coal_rates_info(enabled, r_thr, launches)) }
 int lcx_coal_rates_read(lcx_particles *h, double *out, size_t stride, int out_on_device, int reset)
 { LCX_TRY(H->coal_rates_read(out, stride, out_on_device != 0, reset != 0)) }
+// ---- the collision log (include/lcx_coal_log.h) ----
+int lcx_coal_log_check(size_t capacity, double r_min)
+{
+  std::string err;
+  if (lcx::coal_log::validate(capacity, r_min, err)) return 0;
+  g_err = err;
+  return 1;
+}
+int lcx_coal_log_enable(lcx_particles *h, size_t capacity, double r_min) { LCX_TRY(H->coal_log_enable(capacity, r_min)) }
+int lcx_coal_log_disable(lcx_particles *h) { LCX_TRY(H->coal_log_disable()) }
+int lcx_coal_log_info(lcx_particles *h, int *enabled, size_t *capacity, double *r_min, unsigned long long *held, unsigned long long *seen, unsigned long long *launches)
+{ LCX_TRY(H->coal_log_info(enabled, capacity, r_min, held, seen, launches)) }
+int lcx_coal_log_read(lcx_particles *h, double *out, size_t field_stride, size_t cap_events, int out_on_device, int reset, size_t *n_written, unsigned long long *seen)
+{ LCX_TRY(H->coal_log_read(out, field_stride, cap_events, out_on_device != 0, reset != 0, n_written, seen)) }
 int lcx_diag_coal_rate(lcx_particles *h, int which) { LCX_TRY(H->diag_coal_rate(which)) }
 // ---- move rates per cell (include/lcx_move_rates.h) ----
 int lcx_move_rates_enable(lcx_particles *h, const double *r_thr, int n_thr) { LCX_TRY(H->move_rates_enable(r_thr, n_thr)) }

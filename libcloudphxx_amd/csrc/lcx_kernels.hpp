@@ -16,6 +16,7 @@
 #include "lcx_coal_prevote.hpp"
 #include "lcx_track_plan.hpp"
 #include "lcx_dump_plan.hpp"
+#include "lcx_coal_log_plan.hpp"
 
 namespace lcx {
 
@@ -2674,12 +2675,17 @@ coal_skipped(const coal_own &o, const T scl, const T dt, const u01_src<T> &rs, c
 // One atomic per event and accumulator that the event's row names: the integer sums do not depend on the order, the M3 sums do in their last bits.
 // A rain member's product counts as rain (it is no smaller than the member).
 template <class T, bool TALLY> struct coal_tally_arg {};                          // TALLY == false: nothing travels and nothing is compiled
-template <class T> struct coal_tally_arg<T, true> { unsigned long long *acc; size_t n_cell; T lo; };
+// (acc == nullptr: the TALLY form books no rates; log == nullptr: it logs nothing -- the host launches it when either facility is on)
+template <class T> struct coal_tally_arg<T, true> {
+  unsigned long long *acc; size_t n_cell; T lo;
+  // the collision log (include/lcx_coal_log.h): the list's base, its capacity, its cursor, the filter's bound and this launch's index
+  unsigned long long *log; size_t log_cap; unsigned long long *log_cur; T log_lo; unsigned long long log_launch;
+};
 template <class T>
 __device__ __forceinline__ void
 coal_tally_event(const coal_tally_arg<T, true> &ta, const uint32_t cell, const n_t col_no, const n_t m, const T rw2D, const T rw2R, const T rw2_new)
 {
-  if (m == 0) return;                                                              // (a receiver without droplets moves nothing)
+  if (m == 0 || !ta.acc) return;                                                   // (a receiver without droplets moves nothing; only the log is on)
   unsigned long long *row = ta.acc + cell;
   auto num = [&](int w, unsigned long long v) { if (v) atomicAdd(row + size_t(w) * ta.n_cell, v); };
   auto m3 = [&](int w, double v) { unsafeAtomicAdd(reinterpret_cast<double *>(row + size_t(w) * ta.n_cell), v); };
@@ -2693,6 +2699,55 @@ coal_tally_event(const coal_tally_arg<T, true> &ta, const uint32_t cell, const n
   else if (!rainD) { m3(LCX_CR_ACCR_M3, double(col_no) * double(m) * cube(rw2D)); num(LCX_CR_ACCR_NC, cm); }
   else if (!rainR) { m3(LCX_CR_ACCR_M3, double(m) * cube(rw2R)); num(LCX_CR_ACCR_NC, m); num(LCX_CR_SELF_RAIN_N, cm - m); }
   else num(LCX_CR_SELF_RAIN_N, cm);
+}
+// The collision log (include/lcx_coal_log.h): the event itself, appended to one list from the registers that hold it.  Called
+// where coal_tally_event is, by every lane that arrives there (the sites are divergent already, as coal_skipped's is): a ballot of the lanes whose
+// event is logged -- m > 0 and the stored rw2 not below log_lo (0 with r_min == 0) --, ONE atomic of its popcount on the cursor by the first of
+// them, and each writes at the base + its rank among the ballot's bits, where that is below the capacity: the check stands before every store and
+// nothing is written at or past log_cap.  The cursor goes on counting (`seen`).  Rows are field-major (lcx_coal_log_plan.hpp): a wave's events land
+// in consecutive words of each row.  rd3 is read here, ahead of the caller's update of R's, and only by lanes that write.
+template <class T>
+__device__ __forceinline__ void
+coal_log_event(const coal_tally_arg<T, true> &ta, const uint32_t cell, const uint32_t slotD, const uint32_t slotR, const n_t col_no, const n_t nD, const n_t m,
+               const T rw2D, const T rw2R, const T rw2_new, const T *rd3, const T vtD, const T vtR)
+{
+  if (!ta.log) return;
+  const bool logged = m > 0 && !(rw2_new < ta.log_lo);
+  const unsigned long long mask = __ballot(logged);
+  if (!mask) return;
+  const int first = __ffsll((long long)mask) - 1, lane = int(lane_id());
+  unsigned long long base = 0;
+  if (lane == first) base = atomicAdd(ta.log_cur, (unsigned long long)__popcll(mask));
+  base = __shfl(base, first);
+  if (!logged) return;
+  const unsigned long long i = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+  if (i >= ta.log_cap) return;
+  unsigned long long *w = ta.log + i;
+  auto u = [&](int f, unsigned long long v) { w[coal_log::row(f, ta.log_cap)] = v; };
+  auto r = [&](int f, T v) { reinterpret_cast<double *>(w)[coal_log::row(f, ta.log_cap)] = double(v); };
+  u(LCX_CLG_LAUNCH, ta.log_launch); u(LCX_CLG_CELL, cell); u(LCX_CLG_SLOT_D, slotD); u(LCX_CLG_SLOT_R, slotR);
+  u(LCX_CLG_COL_NO, col_no); u(LCX_CLG_N_D, nD); u(LCX_CLG_N_R, m);
+  r(LCX_CLG_RW2_D, rw2D); r(LCX_CLG_RW2_R, rw2R); r(LCX_CLG_RW2_NEW, rw2_new);
+  r(LCX_CLG_RD3_D, rd3[slotD]); r(LCX_CLG_RD3_R, rd3[slotR]); r(LCX_CLG_VT_D, vtD); r(LCX_CLG_VT_R, vtR);
+}
+// lcx_coal_log_read: the held part of every row as doubles, out[f * stride + i]; blockIdx.y is the field.  All held events or none: with less
+// room than held (the host reports it once it has the cursor) nothing is written
+__global__ void k_coal_log_f64(const unsigned long long *log, size_t cap, const unsigned long long *cursor, size_t cap_events, double *out, size_t stride)
+{
+  const size_t i = gid();
+  const unsigned f = blockIdx.y;
+  const unsigned long long seen = *cursor;
+  if (!coal_log::fits(seen, cap, cap_events) || i >= coal_log::held(seen, cap)) return;
+  const unsigned long long *row = log + coal_log::row(int(f), cap);
+  out[size_t(f) * stride + i] = coal_log::is_integer(int(f)) ? double(row[i]) : reinterpret_cast<const double *>(row)[i];
+}
+// ... and behind it: the cursor as the read saw it into cursor[1] for the host, and with `reset` (and a read that fitted) a cleared cursor
+__global__ void k_coal_log_finish(unsigned long long *cursor, size_t cap, size_t cap_events, int reset)
+{
+  if (gid() != 0) return;
+  const unsigned long long seen = cursor[0];
+  cursor[1] = seen;
+  if (reset && coal_log::fits(seen, cap, cap_events)) cursor[0] = 0;
 }
 // the pair itself, from its gathers on.  pre: u and the cell's volume are coal_skipped's (u_pre, dvc_pre)
 template <class T, bool ONISHI, bool TALLY = false>
@@ -2719,7 +2774,10 @@ coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl,
                                                                                // then needs no look at n; the sorted order of this step still holds it)
     const T rw_b = cbrt(col_no * rw2a * sqrt(rw2a) + rw2b * sqrt(rw2b));
     rw2[b] = rw_b * rw_b;
-    if constexpr (TALLY) coal_tally_event<T>(ta, ca, col_no, nb, rw2a, rw2b, rw_b * rw_b);
+    if constexpr (TALLY) {
+      coal_tally_event<T>(ta, ca, col_no, nb, rw2a, rw2b, rw_b * rw_b);
+      coal_log_event<T>(ta, ca, a, b, col_no, na, nb, rw2a, rw2b, rw_b * rw_b, rd3, vta, vtb);
+    }
     rd3[b] = col_no * rd3[a] + rd3[b];
     vt[b] = T(-1);
     if (rc2) rc2[b] = T(-1);                                                 // invalidator, coal.ipp:33-44,527-545
@@ -2731,7 +2789,10 @@ coal_collide(const coal_own &o, const uint32_t a, const uint32_t b, const T scl,
     if (ijk_mark && nb == col_no * na) ijk_mark[b] = DEAD_CELL;
     const T rw_a = cbrt(col_no * rw2b * sqrt(rw2b) + rw2a * sqrt(rw2a));
     rw2[a] = rw_a * rw_a;
-    if constexpr (TALLY) coal_tally_event<T>(ta, ca, col_no, na, rw2b, rw2a, rw_a * rw_a);
+    if constexpr (TALLY) {
+      coal_tally_event<T>(ta, ca, col_no, na, rw2b, rw2a, rw_a * rw_a);
+      coal_log_event<T>(ta, ca, b, a, col_no, nb, na, rw2b, rw2a, rw_a * rw_a, rd3, vtb, vta);
+    }
     rd3[a] = col_no * rd3[b] + rd3[a];
     vt[a] = T(-1);
     if (rc2) rc2[a] = T(-1);

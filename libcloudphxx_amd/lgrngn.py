@@ -561,6 +561,46 @@ def dump_check(clauses=(("all",),), box=None, fields=DUMP_DEFAULT_FIELDS, lib=No
         raise RuntimeError(lib.lcx_last_error().decode())
 
 
+# ---- the collision log (include/lcx_coal_log.h)
+COAL_LOG_FIELDS = ("launch", "cell", "slot_d", "slot_r", "col_no", "n_d", "n_r", "rw2_d", "rw2_r", "rw2_new", "rd3_d", "rd3_r",
+                   "vt_d", "vt_r")                                   # enum LCX_CLG_*, in its order
+
+
+def coal_log_args(capacity, r_min=0.):
+    """(capacity, r_min) as lcx_coal_log_enable takes them: a positive integer and a non-negative, finite number"""
+    if isinstance(capacity, (bool, float)) or int(capacity) != capacity:
+        raise ValueError("libcloudph++: coal_log: capacity must be an integer")
+    cap, r = int(capacity), float(r_min)
+    if cap == 0:
+        raise ValueError("libcloudph++: coal_log: capacity == 0")
+    if not 0 < cap <= (2 ** 64 - 1) // (8 * len(COAL_LOG_FIELDS)):
+        raise ValueError("libcloudph++: coal_log: capacity = %d is outside what a list of %d rows can hold" % (cap, len(COAL_LOG_FIELDS)))
+    if not (r >= 0 and np.isfinite(r)):
+        raise ValueError("libcloudph++: coal_log: r_min must be non-negative and finite")
+    return cap, r
+
+
+def coal_log_check_out(out):
+    """refuses an `out` of coal_log that is no DeviceArray of (len(COAL_LOG_FIELDS), cap_events) doubles with unit stride along the
+    events; returns (cap_events, row stride)"""
+    nf = len(COAL_LOG_FIELDS)
+    if not isinstance(out, DeviceArray) or len(out.shape) != 2 or out.shape[0] != nf or out.shape[1] < 1:
+        raise ValueError("libcloudph++: coal_log: out must be a DeviceArray of shape (%d, cap_events)" % nf)
+    if out.shape[1] > 1 and out.strides[1] != 1:
+        raise ValueError("libcloudph++: coal_log: out must have unit stride along the events")
+    if out.strides[0] < out.shape[1]:
+        raise ValueError("libcloudph++: coal_log: out's row stride is below cap_events")
+    return out.shape[1], out.strides[0]
+
+
+def coal_log_check(capacity, r_min=0., lib=None):
+    """lcx_coal_log_check on the numbers as given; needs no GPU.  Raises the library's text."""
+    lib = lib if lib is not None else _lib.load()
+    if lib.lcx_coal_log_check(C.c_size_t(capacity), C.c_double(r_min)) != 0:
+        lib.lcx_last_error.restype = C.c_char_p
+        raise RuntimeError(lib.lcx_last_error().decode())
+
+
 # ----------------------------------------------------------------------------- user-facing option structs
 class lognormal:
     """Built-in sum of lognormal modes n(ln rd) (common/lognormal.hpp:25-37); evaluated natively,
@@ -1311,6 +1351,44 @@ class particles_t:
         res = {nm: host[f, :w].copy() for f, nm in enumerate(names)}
         res["n_qualifying"], res["stride"] = Q, st
         return res
+
+    # -- the collision log (include/lcx_coal_log.h; no reference counterpart)
+    def coal_log_enable(self, capacity, r_min=0.):
+        """start (or restart, emptied) the list of coalescence events with room for `capacity` of them; r_min > 0 keeps only the events
+        whose product has a wet radius of at least r_min.  Before or after init()"""
+        cap, r = coal_log_args(capacity, r_min)
+        self._chk(self._f("coal_log_enable")(self._h, C.c_size_t(cap), C.c_double(r)))
+
+    def coal_log_disable(self):
+        self._chk(self._f("coal_log_disable")(self._h))
+
+    def coal_log_info(self):
+        """(enabled, capacity, r_min, held, seen, launches): seen counts the logged events since enable or the last resetting read, held =
+        min(seen, capacity) of them are in the list; launches counts coalescence launches since enable"""
+        en, cap, r, held, seen, n = C.c_int(), C.c_size_t(), C.c_double(), C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        self._chk(self._f("coal_log_info")(self._h, C.byref(en), C.byref(cap), C.byref(r), C.byref(held), C.byref(seen), C.byref(n)))
+        return bool(en.value), cap.value, r.value, held.value, seen.value, n.value
+
+    def coal_log(self, reset=False, out=None):
+        """the held events: a dict name (COAL_LOG_FIELDS) -> float64 array of length held, in no particular order (coal_log_info has seen).  With
+        out= (a DeviceArray of the object's device, (len(COAL_LOG_FIELDS), cap_events) doubles with unit stride along the events,
+        cap_events >= held) the rows stay there, row f holding COAL_LOG_FIELDS[f], and the dict holds "n_written" and "seen" only.
+        reset: empty the log behind the read."""
+        nf = len(COAL_LOG_FIELDS)
+        w, seen = C.c_size_t(), C.c_ulonglong()
+        if out is not None:
+            cap_events, stride = coal_log_check_out(out)
+            self._chk(self._f("coal_log_read")(self._h, C.c_void_p(out.ptr), C.c_size_t(stride), C.c_size_t(cap_events), C.c_int(1),
+                                               C.c_int(int(bool(reset))), C.byref(w), C.byref(seen)))
+            return {"n_written": w.value, "seen": seen.value}
+        info = self.coal_log_info()
+        if not info[0]:
+            raise RuntimeError("libcloudph++: coal_log: read while the log is not enabled (lcx_coal_log_enable)")
+        room = max(info[3], 1)
+        host = np.zeros((nf, room), dtype=np.float64)
+        self._chk(self._f("coal_log_read")(self._h, C.c_void_p(host.ctypes.data), C.c_size_t(room), C.c_size_t(room), C.c_int(0),
+                                           C.c_int(int(bool(reset))), C.byref(w), C.byref(seen)))
+        return {nm: host[f, :w.value].copy() for f, nm in enumerate(COAL_LOG_FIELDS)}
 
     def outbuf(self):
         """bytes-like view of n_cell reals (use numpy.frombuffer(..., dtype=real_t), default float64)."""
